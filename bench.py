@@ -19,6 +19,14 @@ Launch: under torchrun (WORLD_SIZE set, it must equal --gpus), or `python bench.
 starts the N ranks itself (one child process per GPU, env:// rendezvous on 127.0.0.1, a wall-clock
 watchdog, exit status of the first failing rank) before anything touches a GPU; --launch-dry-run prints
 the plan.
+A plain run does what the headline figure needs and no more: mesh and layout, warm-up and pre-heat, the
+timed steps of the library's default path, one JSON line (metric, value, unit, ms_per_step, ...).
+--full adds everything else to that line, each with runs of its own: per-kernel HIP-event times and the
+rooflines, the fast-math, staged and pipelined paths, the host-pointer entry, the CPU baseline, the
+implicit-step figure, halo_parity on N GPUs and the recorded convergence runs.
+--dump-outputs DIR writes what the last timed step computed (residual.npy, dtm.npy: float64 rows in the
+mesh's own cell order, every cell or a fixed seeded sample of DUMP_MAX_ROWS cells), so that two builds
+can be compared output for output: the mesh and the seeded state are the same from run to run.
 """
 import argparse
 import json
@@ -77,6 +85,31 @@ def c4_mesh(fa, scale, mult=1, wall=None, farmap=None, topology="hybrid"):
     fm = C4_FARMAP if farmap is None else farmap
     return (fa.UMesh.naca_ogrid(nt, nq, ntri, 20.0, ws, farmap=fm),
             dict(ntheta=nt, nquad=nq, ntri=ntri, wall_spacing=ws, farmap=fm))
+
+
+DUMP_MAX_ROWS = 1000000     # --dump-outputs: 5 float64 per cell (residual 4 + time step 1) = 40 MB at the most
+DUMP_SEED = 1792
+
+
+def dump_cells(ncells):
+    """the cells (numbers in the mesh's own order) whose rows --dump-outputs writes: every cell, or a
+    fixed seeded sample of DUMP_MAX_ROWS of them in increasing order (the same for every run and build)"""
+    if ncells <= DUMP_MAX_ROWS:
+        return np.arange(ncells, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(ncells, DUMP_MAX_ROWS, replace=False)).astype(np.int64)
+
+
+def write_outputs(path, rows, ncells):
+    """rows: (len(dump_cells(ncells)), 5) float64, residual and time step of the dumped cells; returns the
+    line's account of the files"""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "residual.npy"), np.ascontiguousarray(rows[:, :4], dtype=np.float64))
+    np.save(os.path.join(path, "dtm.npy"), np.ascontiguousarray(rows[:, 4], dtype=np.float64))
+    return {"dir": path, "arrays": {"residual": [len(rows), 4], "dtm": [len(rows)]}, "dtype": "float64",
+            "cells": ("all %d cells, mesh order" % ncells if len(rows) == ncells else
+                      "%d of %d cells in mesh order: numpy default_rng(%d).choice without replacement, sorted"
+                      % (len(rows), ncells, DUMP_SEED)),
+            "of": "the last timed step of the primary path (r and dtm as fvhip_compute_residual_device leaves them)"}
 
 
 def sweep_algorithmic_bytes(N, F, Fb):
@@ -400,6 +433,15 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--scale", type=int, default=1, help="divide the C4 mesh dimensions (debug)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: per-kernel times and rooflines, the fast-math, staged and "
+                         "pipelined paths, the host-pointer entry, the CPU baseline, the implicit-step figure, "
+                         "halo_parity (N GPUs), the recorded convergence runs; the --no-* options below and "
+                         "--cpu-sweeps, --implicit-deadline choose among these and mean nothing without --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the residual and time steps the last of them computed to "
+                         "DIR/residual.npy and DIR/dtm.npy (float64, mesh cell order; a fixed seeded sample of "
+                         "%d cells of a larger mesh)" % DUMP_MAX_ROWS)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sweeps", type=int, default=20, help="timed CPU-baseline sweeps (median)")
     ap.add_argument("--no-fast", action="store_true", help="skip the fast-math mode measurement")
@@ -434,6 +476,8 @@ def main():
     env_world = os.environ.get("WORLD_SIZE")
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if env_world is not None and int(env_world) != args.gpus:
         sys.exit("bench.py: WORLD_SIZE=%s from the launcher differs from --gpus %d; refusing to run"
                  % (env_world, args.gpus))
@@ -532,10 +576,12 @@ def main():
         torch.cuda.synchronize()
         sp.synchronize()
 
-    def measure(fast, path="default", preheat_ms=0.0):
+    def measure(fast, path="default", preheat_ms=0.0, kernels=True, dump=False):
         """ms per step (timed region bracketed by barrier + sync, max over ranks) and per-kernel ms;
         preheat_ms: after the warm-up steps, further untimed steps for that long (all ranks run the
-        same count), outside the timed region"""
+        same count), outside the timed region; kernels=False: no per-kernel passes after the timed steps
+        (an empty dict is returned for them); dump=True: measure.outputs holds the dump_cells(N) rows of
+        r and dtm as the last timed step left them (on N GPUs every rank the whole array)"""
         n.fast_math = fast
         tlay = time.time()
         if world > 1:
@@ -588,17 +634,36 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
             dist.barrier()
+        measure.outputs = None
+        if dump:
+            # rows of the dumped cells by their numbers in the mesh: internal row i holds cell gint[i]; a
+            # cell has one owner, the other ranks add 0.0 to its row
+            cells = dump_cells(N)
+            row_of = np.full(N, -1, dtype=np.int64)
+            row_of[gint] = np.arange(len(gint), dtype=np.int64)
+            loc = row_of[cells]
+            mine = torch.tensor(np.nonzero(loc >= 0)[0], dtype=torch.int64, device="cuda")
+            loc = torch.tensor(loc[loc >= 0], dtype=torch.int64, device="cuda")
+            rows = torch.zeros((len(cells), 5), dtype=torch.float64, device="cuda")
+            rows[mine, :4] = dr[loc]
+            rows[mine, 4] = ddt[loc]
+            if dist is not None:
+                dist.all_reduce(rows)
+            measure.outputs = rows.cpu().numpy()
+            del rows, mine, loc
         # per-kernel durations with HIP events on the library's stream (separate pass): an event pair around
         # every launch, and -- for a step that is one launch of one kernel -- one pair around all the steps
         # (the region average has no per-launch event overhead, which inflates kernels of ~20 us, but it
         # counts the dispatch gaps between launches: the smaller of the two is the tighter bound)
-        sp.profile(True)
-        for _ in range(args.steps):
-            step()
-        kt = sp.kernel_times()
-        sp.profile(False)
+        kt = {}
+        if kernels:
+            sp.profile(True)
+            for _ in range(args.steps):
+                step()
+            kt = sp.kernel_times()
+            sp.profile(False)
         region = None
-        if world == 1 and len(kt) == 1 and list(kt.values())[0][1] == args.steps:
+        if kernels and world == 1 and len(kt) == 1 and list(kt.values())[0][1] == args.steps:
             ext = torch.cuda.ExternalStream(sp.stream())
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             sp.synchronize()
@@ -622,6 +687,49 @@ def main():
     def dominant(km):
         k = max(km, key=km.get)
         return k, km[k]
+
+    if not args.full:
+        # the plain run: the primary path's timed steps (after the same warm-up and pre-heat as under
+        # --full) and the line's headline fields, nothing else
+        tpa = time.time()
+        ms_per_step, _, stats = measure(False, preheat_ms=args.preheat_ms, kernels=False,
+                                        dump=args.dump_outputs is not None)
+        phase("path_primary", tpa)
+        if rank == 0:
+            dumped = None
+            if args.dump_outputs is not None:
+                td = time.time()
+                dumped = write_outputs(args.dump_outputs, measure.outputs, N)
+                phase("dump_outputs", td)
+            out = {
+                "metric": "Mfaces/s (flux+residual sweep) + achieved HBM GB/s, 1/2/4/8 MI355X",
+                "value": round(F / (ms_per_step * 1e-3) / 1e6, 3),
+                "unit": "Mfaces/s",
+                "n_gpus": world,
+                "steps": args.steps,
+                "warmup": args.warmup,
+                "ms_per_step": round(ms_per_step, 5),
+                "higher_is_better": True,
+                "scaling": args.scaling,
+                "vs_baseline": None,
+                "dtype": "f64",
+                "full": False,
+                "numerics": args.numerics,
+                "config": {"cells": N, "faces": F, "boundary_faces": Fb, **dims,
+                           "parallelism": "dp%d: %s" % (world, args.partitioner) if world > 1 else "single GPU",
+                           "layout": stats, "setup_s": round(t_setup, 2),
+                           **({"rehearsal_one_gpu": "all ranks on GPU 0, RCCL over sockets: times are not a measurement"}
+                              if args.rehearse_one_gpu else {})},
+                "preheat": measure.preheat,
+                "dump_outputs": dumped,
+                "note": "achieved HBM GB/s, rooflines and every secondary figure: --full",
+                "build": fa._ffi.build_info(),
+                "phases_s": dict(phases, total=round(time.time() - T_PROCESS, 2)),
+            }
+            print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # every path is timed after the same wall-clock pre-heat (--preheat-ms, reported): kernel times
     # fall ~12 % over the first few hundred ms of a cold GPU, and handle set-up between the paths
@@ -666,10 +774,13 @@ def main():
     # pre-heat (untimed, reported): layout set-up between the secondary measurements leaves the GPU
     # idle for ~1 s, and a 20-step timed region (~6 ms) would otherwise run while the clocks ramp
     tpa = time.time()
-    ms_per_step, kernels_ms, stats = measure(False, preheat_ms=args.preheat_ms)
+    ms_per_step, kernels_ms, stats = measure(False, preheat_ms=args.preheat_ms, dump=args.dump_outputs is not None)
     phase("path_primary", tpa)
     preheat = measure.preheat
     region_ms = measure.region_ms
+    dumped = None
+    if rank == 0 and args.dump_outputs is not None:
+        dumped = write_outputs(args.dump_outputs, measure.outputs, N)
 
     halo = None
     if world > 1:
@@ -802,6 +913,9 @@ def main():
             "scaling": args.scaling,
             "vs_baseline": None,
             "dtype": "f64",
+            "full": True,
+            "numerics": args.numerics,
+            "dump_outputs": dumped,
             "data": ("synthetic (generated structured flat-plate quad mesh; seeded perturbed free stream)"
                      if args.numerics == "config3" else
                      "synthetic (generated NACA0012 hybrid mesh: quadrangle boundary layer and wakes, near-isotropic "

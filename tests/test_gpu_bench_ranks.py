@@ -3,7 +3,8 @@ its two ranks itself (no torchrun), each on GPU 0 with its own NCCL_HOSTID so RC
 communicator and torch's) runs over its socket transport. What the driver's multi-GPU run executes runs
 here: the partition, the library's RCCL communicator, the overlapped halo residual, halo_parity (every
 rank's owned rows bitwise against the one-GPU residual), the N-rank implicit step, the max-over-ranks
-timing and rank 0's one JSON line. The times mean nothing (one shared GPU, sockets)."""
+timing and rank 0's one JSON line. The times mean nothing (one shared GPU, sockets). The runs are --full
+ones: halo_parity, the implicit step and the per-kernel figures are not part of a plain run."""
 import json
 import os
 import subprocess
@@ -21,7 +22,7 @@ def test_bench_two_ranks_on_one_gpu(numerics):
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-one-gpu",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-one-gpu", "--full",
                           "--scale", "4", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-fast",
                           "--preheat-ms", "20", "--launch-timeout", "400", "--numerics", numerics],
                          env=env, capture_output=True, text=True, timeout=450)
@@ -47,7 +48,7 @@ def test_bench_eight_ranks_on_one_gpu():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--rehearse-one-gpu",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--rehearse-one-gpu", "--full",
                           "--scale", "4", "--steps", "5", "--warmup", "2", "--no-fast", "--preheat-ms", "20",
                           "--launch-timeout", "400", "--implicit-deadline", "240"],
                          env=env, capture_output=True, text=True, timeout=450)
@@ -76,7 +77,7 @@ def test_bench_baseline_configs_one_gpu(numerics, flux, operator):
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--numerics", numerics, "--scale", "4",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--numerics", numerics, "--scale", "4",
                           "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--no-fast", "--preheat-ms", "20"],
                          env=env, capture_output=True, text=True, timeout=400)
     assert out.returncode == 0, out.stderr[-3000:]

@@ -71,7 +71,7 @@ def main():
             cal += f"; check on k_prep_cells: FETCH {d['FETCH_SIZE']:.0f} KB vs {32 * cells / 1024:.0f} KB read"
     doc = {"workload": workload,
            "method": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE / --pmc SQ_* in separate passes over "
-                     "bench.py; mean per dispatch",
+                     "bench.py --full (every path's kernels); mean per dispatch",
            "calibration": cal, "kernels": kernels}
     with open(os.path.join(out, name + ".json"), "w") as f:
         json.dump(doc, f, indent=1)

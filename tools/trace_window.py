@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Summarise a rocprofv3 kernel trace of bench.py over the TIMED window only.
+"""Summarise a rocprofv3 kernel trace of bench.py --full over the TIMED window only.
 
-bench.py's primary path dispatches its fused residual: warm-up steps, the pre-heat burst, the `steps`
-timed steps, then `steps` more under HIP-event profiling. So the timed region is the kernel's
+bench.py --full's primary path dispatches its fused residual: warm-up steps, the pre-heat burst, the `steps`
+timed steps, then `steps` more under HIP-event profiling (a plain run, without --full, has no such pass: its
+timed steps are the kernel's last `steps` dispatches, not these). So the timed region is the kernel's
 dispatches [-2*steps, -steps) of its last run. Reads <dir>/run_kernel_trace.csv (rocprofv3
 --kernel-trace --output-format csv), prints one JSON object: per-window mean / median / min / max / p90
 of the duration, the whole-run average (what --stats reports), and the dispatch gaps.
@@ -46,7 +47,7 @@ def main():
            "timed_window": s(win), "event_pass_window": s(du[n - steps:]), "all_dispatches": s(du),
            "timed_window_gap_us": {"median": round(float(np.median(gaps)), 3), "max": round(float(gaps.max()), 3)},
            "timed_window_span_ms": round(float((wen[-1] - wst[0]) / 1e6), 4),
-           "note": "timed window = dispatches [-2*steps, -steps) of the kernel (bench.py: timed steps, then the "
+           "note": "timed window = dispatches [-2*steps, -steps) of the kernel (bench.py --full: timed steps, then the "
                    "same number under HIP-event profiling)"}
     print(json.dumps(out, indent=1))
 
