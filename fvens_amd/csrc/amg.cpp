@@ -4,12 +4,61 @@
  *   and the multicolour order of the coarse level. Everything is built in a fixed order (rows ascending),
  *   so the hierarchy and every device sum over it are the same on every run.
  */
-#include "amg.hpp"
+#include "precond_setup.hpp"
 
 #include <algorithm>
 #include <stdexcept>
 
 namespace fvhip {
+
+AmgGraph amgGraphOfRows(std::vector<std::vector<AmgEntry>>& rows)
+{
+	AmgGraph g;
+	g.n = static_cast<int>(rows.size());
+	g.rowptr.assign(rows.size() + 1, 0);
+	g.dblk.resize(rows.size());
+	for(size_t c = 0; c < rows.size(); c++) {
+		g.dblk[c] = static_cast<int>(c);
+		std::sort(rows[c].begin(), rows[c].end());
+		for(const AmgEntry& e : rows[c]) { g.col.push_back(e.col); g.w.push_back(e.w); g.blk.push_back(e.blk); }
+		g.rowptr[c+1] = static_cast<int>(g.col.size());
+	}
+	return g;
+}
+
+/// items 0 .. key.size()-1 grouped by key, ascending within a group: group q = items[start[q] .. start[q+1])
+static void groupBy(const std::vector<int>& key, int ngroups, std::vector<int>& start, std::vector<int>& items)
+{
+	start.assign(static_cast<size_t>(ngroups) + 1, 0);
+	for(const int k : key) start[k + 1]++;
+	for(int q = 0; q < ngroups; q++) start[q+1] += start[q];
+	items.resize(key.size());
+	std::vector<int> pos(start.begin(), start.end() - 1);
+	for(size_t i = 0; i < key.size(); i++) items[pos[key[i]]++] = static_cast<int>(i);
+}
+
+std::vector<int> greedyColouring(const std::vector<int>& rowptr, const std::vector<int>& col, std::vector<int>& start,
+                                 std::vector<int>& rows)
+{
+	const int n = static_cast<int>(rowptr.size()) - 1;
+	std::vector<int> colour(static_cast<size_t>(n), -1), mark;
+	int ncol = 0;
+	for(int a = 0; a < n; a++) {
+		for(int k = rowptr[a]; k < rowptr[a+1]; k++) {
+			const int b = col[k];
+			if(b != a && colour[b] >= 0) {
+				if(static_cast<int>(mark.size()) <= colour[b]) mark.resize(static_cast<size_t>(colour[b]) + 1, -1);
+				mark[colour[b]] = a;
+			}
+		}
+		int c = 0;
+		while(c < static_cast<int>(mark.size()) && mark[c] == a) c++;
+		colour[a] = c;
+		ncol = std::max(ncol, c + 1);
+	}
+	groupBy(colour, ncol, start, rows);
+	return colour;
+}
 
 AmgLevelHost amgCoarsen(const AmgGraph& g, double threshold)
 {
@@ -55,15 +104,7 @@ AmgLevelHost amgCoarsen(const AmgGraph& g, double threshold)
 	AmgLevelHost L;
 	L.n = na;
 	L.agg = agg;
-	// members of each aggregate, ascending
-	L.mstart.assign(static_cast<size_t>(na) + 1, 0);
-	for(int i = 0; i < n; i++) L.mstart[agg[i] + 1]++;
-	for(int a = 0; a < na; a++) L.mstart[a+1] += L.mstart[a];
-	L.members.resize(static_cast<size_t>(n));
-	{
-		std::vector<int> pos(L.mstart.begin(), L.mstart.end() - 1);
-		for(int i = 0; i < n; i++) L.members[pos[agg[i]]++] = i;
-	}
+	groupBy(agg, na, L.mstart, L.members);             // members of each aggregate, ascending
 	// coarse pattern: I and the aggregates of its members' neighbours, ascending
 	L.rowptr.assign(static_cast<size_t>(na) + 1, 0);
 	std::vector<int> tmp;
@@ -109,30 +150,7 @@ AmgLevelHost amgCoarsen(const AmgGraph& g, double threshold)
 		for(const auto& p : pr) L.csrc[pos[p.first]++] = p.second;
 	}
 	for(int k = 0; k < nnz; k++) std::sort(L.csrc.begin() + L.cstart[k], L.csrc.begin() + L.cstart[k+1]);
-	// greedy colouring in row order
-	std::vector<int> colour(static_cast<size_t>(na), -1), mark;
-	int ncol = 0;
-	for(int a = 0; a < na; a++) {
-		for(int k = L.rowptr[a]; k < L.rowptr[a+1]; k++) {
-			const int b = L.col[k];
-			if(b != a && colour[b] >= 0) {
-				if(static_cast<int>(mark.size()) <= colour[b]) mark.resize(static_cast<size_t>(colour[b]) + 1, -1);
-				mark[colour[b]] = a;
-			}
-		}
-		int c = 0;
-		while(c < static_cast<int>(mark.size()) && mark[c] == a) c++;
-		colour[a] = c;
-		ncol = std::max(ncol, c + 1);
-	}
-	L.cstart_colour.assign(static_cast<size_t>(ncol) + 1, 0);
-	for(int a = 0; a < na; a++) L.cstart_colour[colour[a] + 1]++;
-	for(int q = 0; q < ncol; q++) L.cstart_colour[q+1] += L.cstart_colour[q];
-	L.cells.resize(static_cast<size_t>(na));
-	{
-		std::vector<int> pos(L.cstart_colour.begin(), L.cstart_colour.end() - 1);
-		for(int a = 0; a < na; a++) L.cells[pos[colour[a]]++] = a;
-	}
+	greedyColouring(L.rowptr, L.col, L.cstart_colour, L.cells);
 	return L;
 }
 

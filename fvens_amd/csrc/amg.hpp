@@ -27,38 +27,9 @@
 
 #include <hip/hip_runtime.h>
 #include <vector>
+#include "precond_setup.hpp"   // the host side: AmgGraph, AmgLevelHost, amgCoarsen
 
 namespace fvhip {
-
-/// one coarse level as built on the host
-struct AmgLevelHost
-{
-	int n = 0;                               ///< block rows
-	std::vector<int> rowptr, col, dpos;      ///< block CSR (columns ascending, diagonal included; dpos = its position)
-	std::vector<int> cstart, csrc;           ///< per nonzero: contributing blocks of the finer level (ascending)
-	std::vector<int> mstart, members;        ///< per row: the finer level's rows aggregated into it (ascending)
-	std::vector<int> agg;                    ///< per row of the finer level: its aggregate (row of this level)
-	std::vector<int> cstart_colour, cells;   ///< multicolour order: rows of colour q = cells[cstart_colour[q]..]
-	std::vector<double> w;                   ///< coupling per nonzero (aggregation of the next level)
-};
-
-/// the finer level seen by the aggregation: rows, adjacency with couplings (symmetric), and the block index
-/// of each nonzero of the finer operator (finest: diag c -> c, A[R][L] = lower fi -> n + fi, A[L][R] = upper
-/// fi -> n + Fi + fi; coarse: the CSR position)
-struct AmgGraph
-{
-	int n = 0;
-	std::vector<int> rowptr, col;            ///< off-diagonal adjacency, columns ascending
-	std::vector<double> w;                   ///< coupling per adjacency entry
-	std::vector<int> blk;                    ///< block index of A[row][col] per adjacency entry
-	std::vector<int> dblk;                   ///< block index of A[row][row]
-};
-
-/// aggregates graph g (threshold: strength relative to both cells' strongest coupling) and builds the
-/// coarse level: pattern, Galerkin contribution lists, member lists, colouring, coarse couplings
-AmgLevelHost amgCoarsen(const AmgGraph& g, double threshold);
-/// the graph of a built coarse level (for the next aggregation)
-AmgGraph amgGraphOf(const AmgLevelHost& L);
 
 /// device arrays of one coarse level
 struct AmgLevel

@@ -31,8 +31,6 @@
 #include <memory>
 #include <functional>
 #include <array>
-#include <deque>
-#include <numeric>
 
 #include "krylov.hpp"
 
@@ -723,59 +721,13 @@ struct fvhip_ctx
 		return surf.emplace(marker, c).first->second;
 	}
 
-	/// multicolour block Gauss-Seidel (fvhip_implicit_config::prec_gs): greedy colouring of the owned
-	/// cells in internal (Hilbert) order over interior faces; ghost cells are not coloured (within a
-	/// sweep they hold the values of the last exchange)
+	/// multicolour order of block Gauss-Seidel (fvhip_implicit_config::prec_gs) and ILU(0), built on first use
+	/// (precond_setup.hpp colourCells)
 	std::vector<int> gs_colour_start;
 	std::vector<int> gs_colour;          ///< colour of every owned cell (also the ILU(0) order)
 	long long gs_triples = 0;            ///< owned cells sharing faces pairwise three at a time (ILU(0) fill off the diagonal)
-	int* d_gs_cells = nullptr;
-	int* d_gs_colour = nullptr;
-	void ensureColouring() {
-		if(d_gs_cells) return;
-		const int N = L.ncell;
-		auto nbr = [&](int c, int j) {        // owned neighbour across interior face j of c, else -1
-			const int code = L.cell_rfaces[4*static_cast<size_t>(c)+j];
-			if(code < 0 || (code >> 1) < L.nbface) return -1;
-			const int nb = L.cell_nbr_fo[4*static_cast<size_t>(c)+j];
-			return (nb >= 0 && nb < N) ? nb : -1;
-		};
-		gs_triples = 0;
-		for(int c = 0; c < N; c++)
-			for(int j = 0; j < 4; j++) {
-				const int a = nbr(c, j);
-				if(a <= c) continue;
-				for(int k = j + 1; k < 4; k++) {
-					const int b = nbr(c, k);
-					if(b <= c) continue;
-					for(int m = 0; m < 4; m++) if(nbr(a, m) == b) gs_triples++;
-				}
-			}
-		std::vector<int> col(static_cast<size_t>(N), -1);
-		int ncol = 0;
-		for(int c = 0; c < N; c++) {
-			unsigned long long used = 0;
-			for(int j = 0; j < 4; j++) {
-				const int code = L.cell_rfaces[4*static_cast<size_t>(c)+j];
-				if(code < 0 || (code >> 1) < L.nbface) continue;
-				const int nb = L.cell_nbr_fo[4*static_cast<size_t>(c)+j];
-				if(nb >= 0 && nb < N && col[nb] >= 0) used |= 1ull << col[nb];
-			}
-			int k = 0;
-			while(used & (1ull << k)) k++;
-			col[c] = k;
-			ncol = std::max(ncol, k + 1);
-		}
-		gs_colour_start.assign(static_cast<size_t>(ncol) + 1, 0);
-		for(int c = 0; c < N; c++) gs_colour_start[col[c] + 1]++;
-		for(int k = 0; k < ncol; k++) gs_colour_start[k+1] += gs_colour_start[k];
-		std::vector<int> cells(static_cast<size_t>(std::max(N, 1)));
-		std::vector<int> pos(gs_colour_start.begin(), gs_colour_start.end() - 1);
-		for(int c = 0; c < N; c++) cells[pos[col[c]]++] = c;   // ascending within a colour
-		d_gs_cells = upload(cells, owned);
-		d_gs_colour = upload(col, owned);
-		gs_colour = std::move(col);
-	}
+	int *d_gs_cells = nullptr, *d_gs_colour = nullptr;
+	void ensureColouring();                  // these three: implicit.cpp
 	/// block ILU(0) factorisation in colour order (fvhip_implicit_config::prec_ilu): dinv = the inverted
 	/// pivot blocks Dt^-1, colour after colour (each colour reads the earlier colours' pivots)
 	void iluFactor(const double* diag, const double* lower, const double* upper, double* dinv, hipStream_t st = nullptr) {
@@ -792,240 +744,19 @@ struct fvhip_ctx
 	}
 
 	/// lines of the line-implicit preconditioner (fvhip_implicit_config::prec_lines), built on first use
-	/// from the mesh: coupling of a cell to a neighbour across an interior face = face length / centre
-	/// distance (what dominates the Jacobian blocks of thin cells). A cell is anisotropic if its
-	/// strongest coupling is at least `thr` times its weakest; lines start at the most anisotropic
-	/// unassigned cell and grow at both ends through the end cell's strongest unassigned owned
-	/// neighbour while that neighbour is anisotropic and the link is one of its own two strongest
-	/// (Mavriplis' line construction); every other cell is a line of one. Lines are sorted by length
-	/// so that a wave's threads walk lines of similar length.
+	/// from the mesh (precond_setup.hpp buildLines)
 	LineSet lines{};
 	double lines_thr = -1.0;
 	std::vector<int> h_line_start, h_line_cells, h_line_faces;   ///< the lines in line order (fvhip_lines)
-	void ensureLines(double thr) {
-		if(!(thr >= 0.0) || !std::isfinite(thr)) throw std::invalid_argument("line_threshold must be finite and >= 0 (0: 4)");
-		if(thr == 0.0) thr = 4.0;
-		if(lines.gstart && lines_thr == thr) return;
-		// a rebuild (another threshold) releases the previous line set's device arrays
-		for(const void* p : {static_cast<const void*>(lines.gstart), static_cast<const void*>(lines.cell),
-		                     static_cast<const void*>(lines.face), static_cast<const void*>(lines.D),
-		                     static_cast<const void*>(lines.Lb), static_cast<const void*>(lines.W),
-		                     static_cast<const void*>(lines.len),
-		                     static_cast<const void*>(lines.G), static_cast<const void*>(lines.zpart)}) release(p);
-		lines = LineSet{};
-		const int N = L.ncell, nb = L.nbface;
-		struct Nb { int c, fi; double w; };
-		std::vector<std::array<Nb,4>> nbr(static_cast<size_t>(N));
-		std::vector<int> nn(static_cast<size_t>(N), 0);
-		std::vector<double> ratio(static_cast<size_t>(N), 1.0);
-		for(int c = 0; c < N; c++) {
-			double wmax = 0, wmin = INFINITY;
-			for(int j = 0; j < 4; j++) {
-				const int code = L.cell_rfaces[4*static_cast<size_t>(c)+j];
-				if(code < 0 || (code >> 1) < nb) continue;           // boundary face
-				const int fi = (code >> 1) - nb;
-				const int o = L.cell_nbr_fo[4*static_cast<size_t>(c)+j];
-				const double dx = L.rc[2*static_cast<size_t>(c)] - L.rc[2*static_cast<size_t>(o)];
-				const double dy = L.rc[2*static_cast<size_t>(c)+1] - L.rc[2*static_cast<size_t>(o)+1];
-				const double w = L.if_len[fi]/std::sqrt(dx*dx + dy*dy);
-				wmax = std::max(wmax, w); wmin = std::min(wmin, w);
-				if(o < N) nbr[c][nn[c]++] = Nb{o, fi, w};
-			}
-			std::sort(nbr[c].begin(), nbr[c].begin() + nn[c], [](const Nb& a, const Nb& b) {
-				return a.w > b.w || (a.w == b.w && a.c < b.c); });
-			if(wmin < INFINITY && wmin > 0) ratio[c] = wmax/wmin;
-		}
-		auto strong2 = [&](int c, int o) {               // o among c's two strongest owned neighbours
-			for(int j = 0; j < std::min(nn[c], 2); j++) if(nbr[c][j].c == o) return true;
-			return false;
-		};
-		std::vector<int> order(static_cast<size_t>(N));
-		std::iota(order.begin(), order.end(), 0);
-		std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return ratio[a] > ratio[b]; });
-		std::vector<char> used(static_cast<size_t>(N), 0);
-		std::vector<std::vector<std::pair<int,int>>> all;   // (cell, face to previous) per line
-		for(const int c0 : order) {
-			if(used[c0]) continue;
-			used[c0] = 1;
-			std::deque<std::pair<int,int>> line{{c0, -1}};
-			if(ratio[c0] >= thr) {
-				for(int dir = 0; dir < 2; dir++) {
-					int e = dir == 0 ? line.back().first : line.front().first;
-					for(;;) {
-						int nxt = -1, fi = -1;
-						for(int j = 0; j < std::min(nn[e], 2); j++) {
-							const Nb& b = nbr[e][j];
-							if(!used[b.c]) { nxt = b.c; fi = b.fi; break; }
-						}
-						if(nxt < 0 || ratio[nxt] < thr || !strong2(nxt, e)) break;
-						used[nxt] = 1;
-						if(dir == 0) line.push_back({nxt, fi});
-						else {                              // prepend: the face now links nxt to e
-							line.front().second = fi;
-							line.push_front({nxt, -1});
-						}
-						e = nxt;
-					}
-				}
-			}
-			// lines longer than LINE_MAX_CELLS are cut into pieces: the recurrence along a line is
-			// sequential, so one line of thousands of cells (circumferential lines of the outer O-grid
-			// layers) would set the whole sweep's time
-			for(size_t b = 0; b < line.size(); b += LINE_MAX_CELLS) {
-				const size_t e = std::min(line.size(), b + static_cast<size_t>(LINE_MAX_CELLS));
-				std::vector<std::pair<int,int>> piece(line.begin() + b, line.begin() + e);
-				piece[0].second = -1;
-				all.push_back(std::move(piece));
-			}
-		}
-		// longest first; lines of equal length in ascending internal (Hilbert) order of their first cell, so
-		// that the 64 lanes of a group walk neighbouring lines side by side: their k-th cells' rows of v and
-		// z share 128-byte lines (the cells are gathered by index), instead of 64 unrelated places of the mesh.
-		// Each line's recurrence is independent of the lane it runs on: the same z bit for bit.
-		std::stable_sort(all.begin(), all.end(), [](const std::vector<std::pair<int,int>>& a,
-		                                            const std::vector<std::pair<int,int>>& b) {
-			return a.size() > b.size() || (a.size() == b.size() && a[0].first < b[0].first); });
-		// lanes: a line of at least LINE_TWIST_MIN cells is solved from both ends (twisted factorisation):
-		// its top half t = (n-1)/2 cells in order, then the twist cell t, on lane j of a twisted group; its
-		// bottom half n-1 .. t+1 in reverse order, then t, on lane j+32. Every other line is one lane of a
-		// group of 64. Entries (cell, interior face to the previous entry); rows line-interleaved
-		// (krylov.hpp LineSet)
-		const int nl = static_cast<int>(all.size());
-		int ntw = 0;
-		while(ntw < nl && static_cast<int>(all[static_cast<size_t>(ntw)].size()) >= LINE_TWIST_MIN) ntw++;
-		typedef std::vector<std::pair<int,int>> Lane;
-		std::vector<std::array<Lane,64>> grp;
-		for(int l0 = 0; l0 < ntw; l0 += 32) {
-			grp.emplace_back();
-			for(int q = 0; q < 32 && l0 + q < ntw; q++) {
-				const auto& ln = all[static_cast<size_t>(l0 + q)];
-				const int n = static_cast<int>(ln.size()), tc = (n - 1)/2;
-				Lane top(ln.begin(), ln.begin() + tc + 1), bot;
-				for(int k = n - 1; k >= tc; k--)
-					bot.push_back({ln[static_cast<size_t>(k)].first, k == n - 1 ? -1 : ln[static_cast<size_t>(k) + 1].second});
-				grp.back()[static_cast<size_t>(q)] = std::move(top);
-				grp.back()[static_cast<size_t>(q) + 32] = std::move(bot);
-			}
-		}
-		const int ntg = static_cast<int>(grp.size());
-		for(int l0 = ntw; l0 < nl; l0 += 64) {
-			grp.emplace_back();
-			for(int q = 0; q < 64 && l0 + q < nl; q++) grp.back()[static_cast<size_t>(q)] = all[static_cast<size_t>(l0 + q)];
-		}
-		const int ng = static_cast<int>(grp.size());
-		std::vector<int> gst(static_cast<size_t>(ng) + 1, 0);
-		for(int g = 0; g < ng; g++) {
-			size_t mx = 0;
-			for(const Lane& ln : grp[static_cast<size_t>(g)]) mx = std::max(mx, ln.size());
-			gst[g+1] = gst[g] + static_cast<int>(mx);
-		}
-		const size_t nslot = 64*static_cast<size_t>(gst[ng]);
-		std::vector<int> cells(std::max<size_t>(nslot, 1), -1), faces(std::max<size_t>(nslot, 1), -1);
-		std::vector<int> lens(std::max<size_t>(64*static_cast<size_t>(ng), 1), 0);
-		for(int g = 0; g < ng; g++)
-			for(size_t lane = 0; lane < 64; lane++) {
-				const Lane& ln = grp[static_cast<size_t>(g)][lane];
-				lens[64*static_cast<size_t>(g) + lane] = static_cast<int>(ln.size());
-				for(size_t k = 0; k < ln.size(); k++) {
-					const size_t slot = (static_cast<size_t>(gst[g]) + k)*64 + lane;
-					cells[slot] = ln[k].first;
-					if(k > 0) {
-						const int fi = ln[k].second, p = ln[k-1].first;
-						faces[slot] = (fi << 1) | (L.if_L[fi] == p ? 0 : 1);
-					}
-				}
-			}
-		// the lines as built (fvhip_lines), longest first
-		h_line_start.assign(1, 0);
-		h_line_cells.clear(); h_line_faces.clear();
-		for(const auto& ln : all) {
-			for(size_t k = 0; k < ln.size(); k++) {
-				h_line_cells.push_back(ln[k].first);
-				h_line_faces.push_back(k > 0 ? (ln[k].second << 1) | (L.if_L[ln[k].second] == ln[k-1].first ? 0 : 1) : -1);
-			}
-			h_line_start.push_back(static_cast<int>(h_line_cells.size()));
-		}
-		lines.twisted_groups = ntg;
-		lines.nlines = nl;
-		lines.ngroups = ng;
-		lines.nrows = gst[ng];
-		lines.gstart = upload(gst, owned);
-		lines.cell = upload(cells, owned);
-		lines.face = upload(faces, owned);
-		lines.len = upload(lens, owned);
-		const size_t rows = std::max<size_t>(static_cast<size_t>(gst[ng]), 1);
-		lines.D = dalloc(1024*rows, owned);
-		// zeroed once: in a twisted group the factorisation writes the twist row of D for lane j only
-		// (the pivot); k_line_solve's forward prefetch also requests that row for lane j+32 and discards
-		// it, so it must hold defined values, never garbage a later change could start using
-		HC(hipMemsetAsync(lines.D, 0, sizeof(double)*1024*rows, stream));
-		lines.Lb = dalloc(1024*rows, owned);
-		lines.W = dalloc(1024*rows, owned);
-		lines.G = dalloc(256*rows, owned);
-		lines.zpart = dalloc(static_cast<size_t>(std::max(ng, 1)), owned);
-		lines_thr = thr;
-	}
+	void ensureLines(double thr);
 
-	/// aggregation multigrid hierarchy (fvhip_implicit_config::prec_amg), built on first use from the mesh:
-	/// the finest level's graph is the owned cells over interior faces with couplings face length / centre
-	/// distance (ghost couplings dropped: block-Jacobi across ranks), its block indices those of the
-	/// face-ordered Jacobian (diag c, lower N + fi, upper N + Fi + fi); coarsening stops at `levels` levels
-	/// or when a level has fewer than 64 rows or shrinks by less than 1.25
+	/// aggregation multigrid hierarchy (fvhip_implicit_config::prec_amg), built on first use from the mesh
+	/// (precond_setup.hpp amgFineGraph, amgCoarsen); coarsening stops at `levels` levels or when a level has
+	/// fewer than 64 rows or shrinks by less than 1.25
 	std::vector<AmgLevel> amg;
 	int amg_levels = 0;
 	double amg_thr = -1.0;
-	void ensureAmg(int levels, double thr) {
-		if(levels < 2) throw std::invalid_argument("prec_amg: at least 2 levels");
-		if(!(thr >= 0.0 && thr < 1.0)) throw std::invalid_argument("amg_threshold must be in [0, 1)");
-		if(amg_levels == levels && amg_thr == thr) return;
-		if(!amg.empty()) throw std::runtime_error("prec_amg: the hierarchy is built once per handle (same levels and threshold)");
-		const int N = L.ncell, nb = L.nbface, Fi = L.ninface;
-		AmgGraph g;
-		g.n = N;
-		g.rowptr.assign(static_cast<size_t>(N) + 1, 0);
-		g.dblk.resize(static_cast<size_t>(N));
-		std::vector<std::array<double,3>> row;          // (column, coupling, block)
-		for(int c = 0; c < N; c++) {
-			g.dblk[c] = c;
-			row.clear();
-			for(int j = 0; j < 4; j++) {
-				const int code = L.cell_rfaces[4*static_cast<size_t>(c)+j];
-				if(code < 0 || (code >> 1) < nb) continue;
-				const int o = L.cell_nbr_fo[4*static_cast<size_t>(c)+j];
-				if(o < 0 || o >= N) continue;
-				const int fi = (code >> 1) - nb;
-				const double dx = L.rc[2*static_cast<size_t>(c)] - L.rc[2*static_cast<size_t>(o)];
-				const double dy = L.rc[2*static_cast<size_t>(c)+1] - L.rc[2*static_cast<size_t>(o)+1];
-				const int blk = (code & 1) ? N + fi : N + Fi + fi;     // A[c][o]: c = R reads lower, c = L upper
-				row.push_back({static_cast<double>(o), L.if_len[fi]/std::sqrt(dx*dx + dy*dy), static_cast<double>(blk)});
-			}
-			std::sort(row.begin(), row.end());
-			for(const auto& r : row) {
-				g.col.push_back(static_cast<int>(r[0])); g.w.push_back(r[1]); g.blk.push_back(static_cast<int>(r[2]));
-			}
-			g.rowptr[c+1] = static_cast<int>(g.col.size());
-		}
-		for(int l = 1; l < levels; l++) {
-			if(g.n < 64) break;
-			AmgLevelHost H = amgCoarsen(g, thr);
-			if(H.n*5 > g.n*4) break;                         // shrinks by less than 1.25: stop
-			AmgLevel D;
-			D.n = H.n; D.nnz = H.rowptr[H.n]; D.nfine = g.n;
-			D.rowptr = upload(H.rowptr, owned); D.col = upload(H.col, owned); D.dpos = upload(H.dpos, owned);
-			D.cstart = upload(H.cstart, owned); D.csrc = upload(H.csrc, owned);
-			D.mstart = upload(H.mstart, owned); D.members = upload(H.members, owned); D.agg = upload(H.agg, owned);
-			D.cells = upload(H.cells, owned); D.cstart_colour = H.cstart_colour;
-			D.d_cstart_colour = upload(H.cstart_colour, owned);
-			D.val = dalloc(16*static_cast<size_t>(D.nnz), owned); D.dinv = dalloc(16*static_cast<size_t>(D.n), owned);
-			D.x = dalloc(4*static_cast<size_t>(D.n), owned); D.b = dalloc(4*static_cast<size_t>(D.n), owned);
-			D.r = dalloc(4*static_cast<size_t>(D.n), owned);
-			amg.push_back(D);
-			g = amgGraphOf(H);
-		}
-		if(amg.empty()) throw std::runtime_error("prec_amg: the mesh does not coarsen");
-		amg_levels = levels;
-		amg_thr = thr;
-	}
+	void ensureAmg(int levels, double thr);
 	/// Galerkin operators of every coarse level from the finest blocks, and their diagonal inverses
 	void amgSetup(const double* diag, const double* lower, const double* upper) {
 		timed("k_amg_galerkin", [&]{

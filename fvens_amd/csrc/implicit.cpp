@@ -23,6 +23,70 @@
 #include <cmath>
 #include <vector>
 
+// --- the preconditioners' structures on the device: built on the host (precond_setup.hpp), uploaded here ---
+
+void fvhip_ctx::ensureColouring() {
+	if(d_gs_cells) return;
+	Colouring C = colourCells(cellGraph(L));
+	d_gs_cells = upload(C.cells, owned);
+	d_gs_colour = upload(C.colour, owned);
+	gs_triples = C.triples;
+	gs_colour_start = std::move(C.colour_start);
+	gs_colour = std::move(C.colour);
+}
+
+void fvhip_ctx::ensureLines(double thr) {
+	if(!(thr >= 0.0) || !std::isfinite(thr)) throw std::invalid_argument("line_threshold must be finite and >= 0 (0: 4)");
+	if(thr == 0.0) thr = 4.0;
+	if(lines.gstart && lines_thr == thr) return;
+	// a rebuild (another threshold) releases the previous line set's device arrays
+	for(const void* p : std::initializer_list<const void*>{lines.gstart, lines.cell, lines.face, lines.len, lines.D,
+	                                                       lines.Lb, lines.W, lines.G, lines.zpart}) release(p);
+	lines = LineSet{};
+	LinePlan P = buildLines(cellGraph(L), thr);
+	lines.twisted_groups = P.twisted_groups; lines.nlines = P.nlines; lines.ngroups = P.ngroups; lines.nrows = P.nrows;
+	lines.gstart = upload(P.gstart, owned); lines.cell = upload(P.cell, owned);
+	lines.face = upload(P.face, owned); lines.len = upload(P.len, owned);
+	h_line_start = std::move(P.line_start); h_line_cells = std::move(P.line_cells); h_line_faces = std::move(P.line_faces);
+	const size_t rows = std::max<size_t>(static_cast<size_t>(P.nrows), 1);
+	lines.D = dalloc(1024*rows, owned);
+	// zeroed once: in a twisted group the factorisation writes the twist row of D for lane j only
+	// (the pivot); k_line_solve's forward prefetch also requests that row for lane j+32 and discards
+	// it, so it must hold defined values, never garbage a later change could start using
+	HC(hipMemsetAsync(lines.D, 0, sizeof(double)*1024*rows, stream));
+	lines.Lb = dalloc(1024*rows, owned); lines.W = dalloc(1024*rows, owned); lines.G = dalloc(256*rows, owned);
+	lines.zpart = dalloc(static_cast<size_t>(std::max(P.ngroups, 1)), owned);
+	lines_thr = thr;
+}
+
+void fvhip_ctx::ensureAmg(int levels, double thr) {
+	if(levels < 2) throw std::invalid_argument("prec_amg: at least 2 levels");
+	if(!(thr >= 0.0 && thr < 1.0)) throw std::invalid_argument("amg_threshold must be in [0, 1)");
+	if(amg_levels == levels && amg_thr == thr) return;
+	if(!amg.empty()) throw std::runtime_error("prec_amg: the hierarchy is built once per handle (same levels and threshold)");
+	AmgGraph g = amgFineGraph(cellGraph(L));
+	for(int l = 1; l < levels; l++) {
+		if(g.n < 64) break;
+		AmgLevelHost H = amgCoarsen(g, thr);
+		if(H.n*5 > g.n*4) break;                         // shrinks by less than 1.25: stop
+		AmgLevel D;
+		D.n = H.n; D.nnz = H.rowptr[H.n]; D.nfine = g.n;
+		D.rowptr = upload(H.rowptr, owned); D.col = upload(H.col, owned); D.dpos = upload(H.dpos, owned);
+		D.cstart = upload(H.cstart, owned); D.csrc = upload(H.csrc, owned);
+		D.mstart = upload(H.mstart, owned); D.members = upload(H.members, owned); D.agg = upload(H.agg, owned);
+		D.cells = upload(H.cells, owned); D.cstart_colour = H.cstart_colour;
+		D.d_cstart_colour = upload(H.cstart_colour, owned);
+		D.val = dalloc(16*static_cast<size_t>(D.nnz), owned); D.dinv = dalloc(16*static_cast<size_t>(D.n), owned);
+		D.x = dalloc(4*static_cast<size_t>(D.n), owned); D.b = dalloc(4*static_cast<size_t>(D.n), owned);
+		D.r = dalloc(4*static_cast<size_t>(D.n), owned);
+		amg.push_back(D);
+		g = amgGraphOf(H);
+	}
+	if(amg.empty()) throw std::runtime_error("prec_amg: the mesh does not coarsen");
+	amg_levels = levels;
+	amg_thr = thr;
+}
+
 namespace fvhip_detail {
 
 struct System
@@ -131,6 +195,17 @@ struct LinOp
 	int amg_sweeps = 2, amg_coarse = 6, amg_fine = 2;
 	double amg_thr = 0.2;
 	std::vector<const double*> D, Lo, Up;     ///< per handle: diagonal / lower / upper blocks
+	const ArrayOf aux = [this](size_t i) { return S.hs[i]->iw.aux; };   ///< each handle's scratch vectors
+	const ArrayOf t = [this](size_t i) { return S.hs[i]->iw.t; };
+
+	/// the preconditioner's blocks of handle i in the precision it applies them in (prec_single: the fp32
+	/// copies setup() made): f(PrecBlocks); the launch_* overloads select on the pointer type
+	template <typename T> struct PrecBlocks { const T *diag, *dinv, *lo, *up; };
+	template <typename F> void withBlocks(size_t i, F&& f) {
+		const fvhip_ctx::ImplicitWork& w = S.hs[i]->iw;
+		if(single) f(PrecBlocks<float>{w.sdiag, w.sdinv, w.slo, w.sup});
+		else f(PrecBlocks<double>{D[i], w.dinv, Lo[i], Up[i]});
+	}
 
 	/// y = A x with the assembled blocks; x has ghost rows, which are filled here
 	void blocks(const ArrayOf& x, const ArrayOf& y) {
@@ -156,12 +231,10 @@ struct LinOp
 		if(gs) { gaussSeidel(v, z); return; }
 		if(lines) { lineSweeps(v, z, want_norm); return; }
 		if(ilu) { iluSweeps(v, z); return; }
-		const ArrayOf aux = [&](size_t i) { return S.hs[i]->iw.aux; };
 		auto buf = [&](int k) -> const ArrayOf& { return ((sweeps - 1 - k) % 2 == 0) ? z : aux; };
 		S.each([&](size_t i, fvhip_ctx* h) {
 			h->timed("k_bjac_apply", [&]{
-				if(single) launch_bjac_apply(h->L.ncell, h->iw.sdinv, v(i), buf(0)(i), h->stream);
-				else launch_bjac_apply(h->L.ncell, h->iw.dinv, v(i), buf(0)(i), h->stream);
+				withBlocks(i, [&](auto B) { launch_bjac_apply(h->L.ncell, B.dinv, v(i), buf(0)(i), h->stream); });
 			});
 		});
 		for(int k = 1; k < sweeps; k++) {
@@ -170,11 +243,16 @@ struct LinOp
 			S.exchange(zin, 4);
 			S.each([&](size_t i, fvhip_ctx* h) {
 				h->timed("k_bjac_sweep", [&]{
-					if(single) launch_bjac_sweep(h->J, h->iw.sdinv, h->iw.slo, h->iw.sup, v(i), zin(i), zout(i), h->stream);
-					else launch_bjac_sweep(h->J, h->iw.dinv, Lo[i], Up[i], v(i), zin(i), zout(i), h->stream);
+					withBlocks(i, [&](auto B) { launch_bjac_sweep(h->J, B.dinv, B.lo, B.up, v(i), zin(i), zout(i), h->stream); });
 				});
 			});
 		}
+	}
+	/// colour `col` of handle i's block Gauss-Seidel sweep on A z = v, in place on z
+	void sweepColour(size_t i, int col, const double* v, double* z) {
+		fvhip_ctx* h = S.hs[i];
+		const int b = h->gs_colour_start[col], n = h->gs_colour_start[col+1] - b;
+		withBlocks(i, [&](auto B) { launch_bgs_colour(h->J, B.dinv, B.lo, B.up, v, z, h->d_gs_cells + b, n, h->stream); });
 	}
 	/// z = M^-1 v by `sweeps` multicolour block Gauss-Seidel sweeps from z = 0, colours in forward
 	/// then backward order on alternate sweeps (symmetric Gauss-Seidel pairs). Across ranks the
@@ -190,12 +268,7 @@ struct LinOp
 			S.each([&](size_t i, fvhip_ctx* h) {
 				const int nc = static_cast<int>(h->gs_colour_start.size()) - 1;
 				h->timed("k_bgs_colour", [&]{
-					for(int q = 0; q < nc; q++) {
-						const int col = fwd ? q : nc - 1 - q;
-						const int b = h->gs_colour_start[col], n = h->gs_colour_start[col+1] - b;
-						if(single) launch_bgs_colour(h->J, h->iw.sdinv, h->iw.slo, h->iw.sup, v(i), z(i), h->d_gs_cells + b, n, h->stream);
-						else launch_bgs_colour(h->J, h->iw.dinv, Lo[i], Up[i], v(i), z(i), h->d_gs_cells + b, n, h->stream);
-					}
+					for(int q = 0; q < nc; q++) sweepColour(i, fwd ? q : nc - 1 - q, v(i), z(i));
 				});
 			});
 		}
@@ -211,19 +284,12 @@ struct LinOp
 			h->timed("k_ilu_solve", [&]{
 				// forward over colours 0..nc-1, backward over nc-2..0: the last colour's backward value
 				// would be its forward one again (all its neighbours are of earlier colours)
-				for(int q = 0; q < 2*nc - 1; q++) {
-					const int col = q < nc ? q : 2*nc - 2 - q;
-					const int b = h->gs_colour_start[col], n = h->gs_colour_start[col+1] - b;
-					if(single) launch_bgs_colour(h->J, h->iw.sdinv, h->iw.slo, h->iw.sup, v(i), z(i), h->d_gs_cells + b, n, h->stream);
-					else launch_bgs_colour(h->J, h->iw.dinv, Lo[i], Up[i], v(i), z(i), h->d_gs_cells + b, n, h->stream);
-				}
+				for(int q = 0; q < 2*nc - 1; q++) sweepColour(i, q < nc ? q : 2*nc - 2 - q, v(i), z(i));
 			});
 		});
 	}
 	/// ILU(0), then `sweeps` - 1 corrections z += M^-1 (v - A z) (A with the ghost coupling)
 	void iluSweeps(const ArrayOf& v, const ArrayOf& z) {
-		const ArrayOf aux = [&](size_t i) { return S.hs[i]->iw.aux; };
-		const ArrayOf t = [&](size_t i) { return S.hs[i]->iw.t; };
 		iluApply(v, z);
 		for(int k = 1; k < sweeps; k++) {
 			blocks(z, t);
@@ -235,8 +301,6 @@ struct LinOp
 	/// z = M^-1 v with M the block-tridiagonal line part of A (factorised in setup), then `sweeps` - 1
 	/// corrections z += M^-1 (v - A z) (A with the ghost coupling: block-Jacobi across ranks)
 	void lineSweeps(const ArrayOf& v, const ArrayOf& z, bool want_norm = false) {
-		const ArrayOf aux = [&](size_t i) { return S.hs[i]->iw.aux; };
-		const ArrayOf t = [&](size_t i) { return S.hs[i]->iw.t; };
 		// one sweep on one domain for the matrix-free operator: the line solve also returns |z|^2
 		const bool norm = want_norm && matfree && sweeps == 1 && S.size() == 1 && !S.exg && !S.halo();
 		S.each([&](size_t i, fvhip_ctx* h) {
@@ -255,16 +319,14 @@ struct LinOp
 	/// z = the finest smoother applied to v (line solve, else D^-1 v)
 	void smooth0(fvhip_ctx* h, size_t i, const double* v, double* z) {
 		if(lines) h->timed("k_line_solve", [&]{ launch_line_solve(h->lines, v, z, h->stream); });
-		else if(single) launch_bjac_apply(h->L.ncell, h->iw.sdinv, v, z, h->stream);
-		else launch_bjac_apply(h->L.ncell, h->iw.dinv, v, z, h->stream);
+		else withBlocks(i, [&](auto B) { launch_bjac_apply(h->L.ncell, B.dinv, v, z, h->stream); });
 	}
 	/// t = v - A z (A with the ghost coupling)
 	void residual0(const ArrayOf& v, const ArrayOf& z, const ArrayOf& t) {
 		S.exchange(z, 4);
 		S.each([&](size_t i, fvhip_ctx* h) {
 			h->timed("k_block_residual", [&]{
-				if(single) launch_block_residual(h->J, h->iw.sdiag, h->iw.slo, h->iw.sup, z(i), v(i), t(i), h->stream);
-				else launch_block_residual(h->J, D[i], Lo[i], Up[i], z(i), v(i), t(i), h->stream);
+				withBlocks(i, [&](auto B) { launch_block_residual(h->J, B.diag, B.lo, B.up, z(i), v(i), t(i), h->stream); });
 			});
 		});
 	}
@@ -296,8 +358,6 @@ struct LinOp
 	/// z = M^-1 v, M one V-cycle of the aggregation multigrid (block-Jacobi across ranks: each handle's hierarchy
 	/// covers its owned cells; the finest residuals include the ghost coupling)
 	void amgApply(const ArrayOf& v, const ArrayOf& z) {
-		const ArrayOf aux = [&](size_t i) { return S.hs[i]->iw.aux; };
-		const ArrayOf t = [&](size_t i) { return S.hs[i]->iw.t; };
 		S.each([&](size_t i, fvhip_ctx* h) { smooth0(h, i, v(i), z(i)); });
 		auto correct = [&]() {             // z += M0^-1 (v - A z)
 			residual0(v, z, t);
@@ -314,50 +374,33 @@ struct LinOp
 		});
 		for(int k = 0; k < amg_fine; k++) correct();
 	}
-	/// block inverses of the current diagonal blocks (or the line factorisation)
+	/// the preconditioner of the current blocks: the line factorisation or the (ILU) diagonal inverses -- with
+	/// the multigrid, its finest smoother -- their fp32 copies, and the multigrid's coarse operators.
+	/// (The entry points refuse prec_lines with prec_gs / prec_ilu, and the multigrid with either.)
 	void setup() {
-		if(amg) {
-			S.each([&](size_t i, fvhip_ctx* h) {
-				if(lines) {
-					h->ensureLines(line_thr);
-					h->lines.single = single;
-					h->timed("k_line_factor", [&]{ launch_line_factor(h->lines, D[i], Lo[i], Up[i], h->stream); });
-				} else h->timed("k_bjac_invert", [&]{ launch_bjac_invert(h->L.ncell, D[i], h->iw.dinv, h->stream); });
-				if(single) {                  // fp32 copies of the finest operator for the smoother's residuals
-					h->ensureSinglePrecond();
-					const long long nf = 16LL*std::max(h->L.ninface, 0);
-					h->timed("k_to_single", [&]{
-						launch_to_single(16LL*h->L.ncell, D[i], h->iw.sdiag, h->stream);
-						launch_to_single(nf, Lo[i], h->iw.slo, h->stream);
-						launch_to_single(nf, Up[i], h->iw.sup, h->stream);
-						if(!lines) launch_to_single(16LL*h->L.ncell, h->iw.dinv, h->iw.sdinv, h->stream);
-					});
-				}
-				h->ensureAmg(amg, amg_thr);
-				h->amgSetup(D[i], Lo[i], Up[i]);
-			});
-			return;
-		}
 		S.each([&](size_t i, fvhip_ctx* h) {
+			const fvhip_ctx::ImplicitWork& w = h->iw;
 			if(lines) {
 				h->ensureLines(line_thr);
 				h->lines.single = single;
 				h->timed("k_line_factor", [&]{ launch_line_factor(h->lines, D[i], Lo[i], Up[i], h->stream); });
-				return;
-			}
-			if(ilu) h->iluFactor(D[i], Lo[i], Up[i], h->iw.dinv);
-			else h->timed("k_bjac_invert", [&]{ launch_bjac_invert(h->L.ncell, D[i], h->iw.dinv, h->stream); });
+			} else if(ilu) h->iluFactor(D[i], Lo[i], Up[i], w.dinv);
+			else h->timed("k_bjac_invert", [&]{ launch_bjac_invert(h->L.ncell, D[i], w.dinv, h->stream); });
 			if(gs) h->ensureColouring();
-			if(single) {
+			if(single && (amg || !lines)) {      // (the line factors are stored in fp32 by the factorisation itself)
 				h->ensureSinglePrecond();
-				const long long nf = 16LL*std::max(h->L.ninface, 0);
+				const long long nd = 16LL*h->L.ncell, nf = 16LL*std::max(h->L.ninface, 0);
+				auto convert = [&](long long n, const double* a, float* b) { launch_to_single(n, a, b, h->stream); };
 				h->timed("k_to_single", [&]{
-					launch_to_single(16LL*h->L.ncell, h->iw.dinv, h->iw.sdinv, h->stream);
-					if(sweeps > 1 || gs || ilu) {
-						launch_to_single(nf, Lo[i], h->iw.slo, h->stream);
-						launch_to_single(nf, Up[i], h->iw.sup, h->stream);
-					}
+					if(amg) convert(nd, D[i], w.sdiag);      // the finest operator, for the smoother's residuals
+					else convert(nd, w.dinv, w.sdinv);
+					if(amg || sweeps > 1 || gs || ilu) { convert(nf, Lo[i], w.slo); convert(nf, Up[i], w.sup); }
+					if(amg && !lines) convert(nd, w.dinv, w.sdinv);
 				});
+			}
+			if(amg) {
+				h->ensureAmg(amg, amg_thr);
+				h->amgSetup(D[i], Lo[i], Up[i]);
 			}
 		});
 	}

@@ -346,7 +346,7 @@ __device__ __forceinline__ void stP16(float* __restrict__ X, long long r, int j,
 /// and D, Lb, W stored pair-interleaved for the solve. The next cell's blocks are requested before the
 /// current cell's arithmetic (their addresses do not depend on it) and the cell/face codes two cells
 /// ahead, so the recurrence does not wait a memory round trip per cell.
-/// Twisted groups (g < twisted_groups; ctx.hpp ensureLines): lane j walks the top half of line j and
+/// Twisted groups (g < twisted_groups; precond_setup.cpp buildLines): lane j walks the top half of line j and
 /// lane j+32 the bottom half backwards, each list ending in the twist cell t. A half stops at t with the
 /// Schur term S = A[t][last] W_last of its side instead of a pivot; the two lanes swap S and lane j
 /// stores the twist pivot (A_tt - S_top - S_bottom)^-1 in its row of t. That is the same block

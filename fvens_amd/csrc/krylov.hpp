@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include "gasdyn.hpp"
+#include "precond_setup.hpp"
 
 namespace fvhip {
 
@@ -64,14 +65,8 @@ struct LineSet {
 	double* zpart = nullptr;         ///< [ngroups] per-group sums of z.z (launch_line_solve with a norm)
 	bool single = false;             ///< D, Lb, W held in fp32 (prec_single; float4 rows in the same buffers)
 };
-#ifndef FVHIP_LINE_MAX
-#define FVHIP_LINE_MAX 256
-#endif
-constexpr int LINE_MAX_CELLS = FVHIP_LINE_MAX;   ///< longest line piece (ctx.hpp ensureLines)
-#ifndef FVHIP_LINE_TWIST_MIN
-#define FVHIP_LINE_TWIST_MIN 16
-#endif
-constexpr int LINE_TWIST_MIN = FVHIP_LINE_TWIST_MIN;   ///< shortest line solved from both ends
+// LINE_MAX_CELLS (longest line piece) and LINE_TWIST_MIN (shortest line solved from both ends):
+// precond_setup.hpp, where buildLines cuts and packs the lines
 /// block-Thomas factorisation of every line (D, Lb, W of the line set) from the block operator
 void launch_line_factor(const LineSet& Ls, const double* diag, const double* lower, const double* upper, hipStream_t s);
 /// z = (block-tridiagonal line part of A)^-1 v; with zsq, also zsq[0] = z.z over the solved rows (each

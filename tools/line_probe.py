@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Probe: the line-implicit preconditioner's line set on a mesh (ctx.hpp ensureLines): number of lines,
+"""Probe: the line-implicit preconditioner's line set on a mesh (precond_setup.cpp buildLines): number of lines,
 length distribution, how they fill the lane groups of k_line_factor / k_line_solve (lines of >= 16 cells
 solved from both ends, 32 per group; others 64 per group, a group's rows = its longest lane), and the
 rows x 64 lane slots the kernels walk against the cells they hold. One GPU (the line set is built by the
