@@ -93,6 +93,9 @@ class ImplicitConfig:
     amg_threshold: float = 0.2      # aggregation strength threshold (-pc_gamg_threshold)
     amg_fine_sweeps: int = 0        # finest-level smoothing sweeps (0: amg_sweeps)
     resume: tuple = None            # continue a checkpointed solve: (first residual, last, the one before, last CFL)
+    amg_smoother: int = 0           # coarse-level smoother: 0 colour Gauss-Seidel over the level, 1 block-Jacobi between
+    #                                 row blocks with Gauss-Seidel inside (-mg_levels_pc_type bjacobi -mg_levels_sub_pc_type sor)
+    amg_block_rows: int = 0         # rows per block of amg_smoother 1 (multiple of 64 in [64, 2048]; 0: the default)
 
     def _struct(self):
         c = _ffi.FvImplicitConfig()
@@ -109,6 +112,7 @@ class ImplicitConfig:
         c.prec_amg, c.amg_sweeps, c.amg_coarse_sweeps = int(self.prec_amg), int(self.amg_sweeps), int(self.amg_coarse_sweeps)
         c.amg_threshold = float(self.amg_threshold)
         c.amg_fine_sweeps = int(self.amg_fine_sweeps)
+        c.amg_smoother, c.amg_block_rows = int(self.amg_smoother), int(self.amg_block_rows)
         if self.resume is not None:
             c.resume_res0, c.resume_res, c.resume_res_prev, c.resume_cfl = (float(x) for x in self.resume)
         return c
@@ -485,6 +489,44 @@ class FlowFV:
         check(_ffi.lib().fvhip_amg_level(self._h, int(level), iptr(n), iptr(nnz), iptr(agg), iptr(rowptr), iptr(col),
                                          dptr(val)))
         return dict(n=int(n[0]), agg=agg, rowptr=rowptr, col=col, val=val)
+
+    def amg_precondition_smoother_device(self, d_diag, d_lower, d_upper, levels=5, threshold=0.2, sweeps=2,
+                                         coarse_sweeps=10, line_threshold=0.0, d_v=None, d_z=None, smoother=0, block_rows=0):
+        """amg_precondition_device with the coarse levels' smoother (ImplicitConfig.amg_smoother) and its rows per
+        block (amg_block_rows; 0: the default)"""
+        nl = np.zeros(1, np.int32)
+        check(_ffi.lib().fvhip_amg_precondition_smoother_device(
+            self._h, *[ctypes.c_void_p(p) for p in (d_diag, d_lower, d_upper)], int(levels), float(threshold), int(sweeps),
+            int(coarse_sweeps), float(line_threshold), ctypes.c_void_p(d_v), ctypes.c_void_p(d_z), iptr(nl), int(smoother),
+            int(block_rows)))
+        return int(nl[0])
+
+    def amg_smooth_level_device(self, level, d_b, d_x, smoother=0, block_rows=0, sweeps=1, direction=0, zero=True):
+        """`sweeps` sweeps of a level smoother on A_level x = b of a hierarchy already set up (amg_precondition_device):
+        smoother 0 colour Gauss-Seidel over the level, 1 block-Jacobi between blocks of block_rows rows with
+        Gauss-Seidel inside; direction 0 forward, 1 backward, 2 alternating; d_x [n][4] is the initial guess (0 and
+        not read if `zero`) and the result"""
+        check(_ffi.lib().fvhip_amg_smooth_level_device(self._h, int(level), int(smoother), int(block_rows), int(sweeps),
+                                                       int(direction), int(bool(zero)), ctypes.c_void_p(d_b),
+                                                       ctypes.c_void_p(d_x)))
+
+    def amg_level_colours(self, level):
+        """colour per row of coarse level `level` (rows of one colour share no block)"""
+        nc, n = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        check(_ffi.lib().fvhip_amg_level(self._h, int(level), iptr(n), None, None, None, None, None))
+        col = np.zeros(int(n[0]), np.int32)
+        check(_ffi.lib().fvhip_amg_level_colours(self._h, int(level), iptr(nc), iptr(col)))
+        return col
+
+    def amg_level_blocks(self, level, block_rows=0):
+        """the block smoother's offsets [nblocks + 1][ncolours] into the level's rows listed colour by colour: the
+        rows of colour q in block k are entries off[k, q] .. off[k + 1, q] - 1 of that list"""
+        nb, nc = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        check(_ffi.lib().fvhip_amg_level_colours(self._h, int(level), iptr(nc), None))
+        check(_ffi.lib().fvhip_amg_level_blocks(self._h, int(level), int(block_rows), iptr(nb), None))
+        off = np.zeros((int(nb[0]) + 1, int(nc[0])), np.int32)
+        check(_ffi.lib().fvhip_amg_level_blocks(self._h, int(level), int(block_rows), iptr(nb), iptr(off)))
+        return off
 
     def colouring(self):
         """(colour per owned cell in internal order, number of pairwise-adjacent cell triples)"""

@@ -43,7 +43,8 @@ class FvImplicitConfig(ctypes.Structure):
                 ("line_threshold", ctypes.c_double), ("prec_ilu", ctypes.c_int), ("cgs_refine", ctypes.c_int),
                 ("prec_amg", ctypes.c_int), ("amg_sweeps", ctypes.c_int), ("amg_coarse_sweeps", ctypes.c_int),
                 ("amg_threshold", ctypes.c_double), ("amg_fine_sweeps", ctypes.c_int), ("resume_res0", ctypes.c_double), ("resume_res", ctypes.c_double),
-                ("resume_res_prev", ctypes.c_double), ("resume_cfl", ctypes.c_double)]
+                ("resume_res_prev", ctypes.c_double), ("resume_cfl", ctypes.c_double),
+                ("amg_smoother", ctypes.c_int), ("amg_block_rows", ctypes.c_int)]
 
 
 class FvSolveStats(ctypes.Structure):
@@ -128,6 +129,12 @@ _SIGS = {
                                                                          ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
                                                                          ctypes.c_void_p, ctypes.c_void_p]),
     "fvhip_amg_level": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 6),
+    "fvhip_amg_precondition_smoother_device": (ctypes.c_int, [ctypes.c_void_p] * 4 + [
+        ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
+    "fvhip_amg_smooth_level_device": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 6 + [ctypes.c_void_p] * 2),
+    "fvhip_amg_level_colours": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_int_p, c_int_p]),
+    "fvhip_amg_level_blocks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_int_p, c_int_p]),
     "fvhip_colouring": (ctypes.c_int, [ctypes.c_void_p, c_int_p, c_int_p, ctypes.POINTER(ctypes.c_longlong)]),
     "fvhip_group_matfree_set_state_device": (ctypes.c_int, [ctypes.c_void_p, _vpp, _vpp, _vpp]),
     "fvhip_group_matfree_apply_device": (ctypes.c_int, [ctypes.c_void_p, _vpp, _vpp]),

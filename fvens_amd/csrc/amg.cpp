@@ -154,6 +154,24 @@ AmgLevelHost amgCoarsen(const AmgGraph& g, double threshold)
 	return L;
 }
 
+std::vector<int> amgBlockOffsets(int n, const std::vector<int>& cstart_colour, const std::vector<int>& cells, int R)
+{
+	if(n <= 0 || R < 1 || cstart_colour.size() < 2 || cstart_colour.back() != n || static_cast<int>(cells.size()) < n)
+		throw std::invalid_argument("amgBlockOffsets: not a level's colour order");
+	const int nc = static_cast<int>(cstart_colour.size()) - 1;
+	const int nb = static_cast<int>((static_cast<long long>(n) + R - 1)/R);
+	std::vector<int> off((static_cast<size_t>(nb) + 1)*static_cast<size_t>(nc));
+	for(int q = 0; q < nc; q++) {
+		const auto first = cells.begin() + cstart_colour[q], last = cells.begin() + cstart_colour[q+1];
+		for(int k = 0; k <= nb; k++) {
+			const long long row0 = static_cast<long long>(k)*R;          // the first row of block k (past the end: n)
+			const auto it = row0 >= n ? last : std::lower_bound(first, last, static_cast<int>(row0));
+			off[static_cast<size_t>(k)*nc + q] = static_cast<int>(it - cells.begin());
+		}
+	}
+	return off;
+}
+
 AmgGraph amgGraphOf(const AmgLevelHost& L)
 {
 	AmgGraph g;

@@ -7,6 +7,8 @@
 #include "amg.hpp"
 #include "blk4.hpp"
 
+#include <stdexcept>
+
 namespace fvhip {
 
 static inline int nblk(long long n, int b) { return static_cast<int>((n + b - 1)/b); }
@@ -164,6 +166,68 @@ void launch_amg_gs_block(const AmgLevel& L, const double* b, double* x, int swee
 	hipLaunchKernelGGL(k_amg_gs_block, dim3(1), dim3(1024), 32*static_cast<size_t>(L.n), s, L.n, static_cast<int>(L.cstart_colour.size()) - 1,
 	                   L.d_cstart_colour, L.cells, L.rowptr, L.col, L.dpos, L.val, L.dinv, b, x, sweeps, fwd ? 1 : 0,
 	                   alternate ? 1 : 0, zero ? 1 : 0);
+}
+
+/// workgroup k: rows [k R, min(n, (k+1) R)) of one sweep xout = S(xin), block-Jacobi between the workgroups' row
+/// blocks, colour Gauss-Seidel inside. The block's rows live in LDS (32 B a row); a column inside the block is
+/// read from there (the value of this sweep once its colour has passed), any other from xin, which nobody
+/// writes during the launch. off: the block's ranges of `cells` per colour (amgBlockOffsets), possibly empty --
+/// the barrier after a colour is outside the row loop, so every thread reaches it. Row update and summation
+/// order are k_amg_gs's. zero: xin = 0, not read
+__global__ __launch_bounds__(1024)
+void k_amg_bjgs(int n, int R, int ncol, const int* __restrict__ off, const int* __restrict__ cells,
+                const int* __restrict__ rowptr, const int* __restrict__ col, const int* __restrict__ dpos,
+                const double* __restrict__ val, const double* __restrict__ dinv, const double* __restrict__ b,
+                const double* __restrict__ xin, double* __restrict__ xout, int fwd, int zero)
+{
+	extern __shared__ __attribute__((aligned(16))) double xs[];
+	const int t = static_cast<int>(threadIdx.x), i = t & 3, nt = static_cast<int>(blockDim.x);
+	const int row0 = static_cast<int>(blockIdx.x)*R;
+	const int rows = min(R, n - row0);
+	const size_t g0 = 4*static_cast<size_t>(row0);
+	for(int k = t; k < 4*rows; k += nt) xs[k] = zero ? 0.0 : xin[g0 + k];
+	__syncthreads();
+	const double4* xs4 = reinterpret_cast<const double4*>(xs);
+	const double4* xg4 = reinterpret_cast<const double4*>(xin);
+	const int* o0 = off + static_cast<size_t>(blockIdx.x)*ncol;
+	const int* o1 = o0 + ncol;
+	for(int qq = 0; qq < ncol; qq++) {
+		const int q = fwd ? qq : ncol - 1 - qq;
+		const int b0 = o0[q], cnt = o1[q] - b0;
+		for(int r0 = 0; r0 < cnt; r0 += nt >> 2) {
+			const int rr = r0 + (t >> 2);
+			const bool live = rr < cnt;
+			const int row = cells[b0 + (live ? rr : cnt - 1)];      // lanes past the end compute a copy and store nothing
+			double acc = b[4*static_cast<size_t>(row) + i];
+			const int kd = dpos[row];
+			for(int k = rowptr[row]; k < rowptr[row+1]; k++) {
+				if(k == kd) continue;
+				const double4 a = reinterpret_cast<const double4*>(val + 16*static_cast<size_t>(k))[i];
+				const int c = col[k], lc = c - row0;
+				double4 xv = make_double4(0.0, 0.0, 0.0, 0.0);
+				if(lc >= 0 && lc < rows) xv = xs4[lc];
+				else if(!zero) xv = xg4[c];
+				acc -= a.x*xv.x + a.y*xv.y + a.z*xv.z + a.w*xv.w;
+			}
+			const double4 s = make_double4(__shfl(acc, 0, 4), __shfl(acc, 1, 4), __shfl(acc, 2, 4), __shfl(acc, 3, 4));
+			const double4 d = reinterpret_cast<const double4*>(dinv + 16*static_cast<size_t>(row))[i];
+			const double o = d.x*s.x + d.y*s.y + d.z*s.z + d.w*s.w;
+			if(live) xs[4*static_cast<size_t>(row - row0) + i] = o;
+		}
+		__syncthreads();
+	}
+	for(int k = t; k < 4*rows; k += nt) xout[g0 + k] = xs[k];
+}
+
+void launch_amg_bjgs(const AmgLevel& L, int R, const int* d_off, const double* b, const double* xin, double* xout,
+                     bool fwd, bool zero, hipStream_t s)
+{
+	if(L.n <= 0) return;
+	if(R < 64 || R > AMG_BLOCK_ROWS || R % 64 != 0 || !d_off || xin == xout)
+		throw std::invalid_argument("launch_amg_bjgs: block rows a multiple of 64 in [64, 2048], xin != xout");
+	hipLaunchKernelGGL(k_amg_bjgs, dim3(nblk(L.n, R)), dim3(R >= 256 ? 1024 : 4*R), 32*static_cast<size_t>(R), s, L.n, R,
+	                   static_cast<int>(L.cstart_colour.size()) - 1, d_off, L.cells, L.rowptr, L.col, L.dpos, L.val, L.dinv,
+	                   b, xin, xout, fwd ? 1 : 0, zero ? 1 : 0);
 }
 
 void launch_amg_galerkin_fine(const AmgLevel& L, int nfine, int nif, const double* diag, const double* lower,

@@ -20,12 +20,15 @@
  * Per Jacobian (each pseudo-time step): the Galerkin sums level by level and the coarse diagonal inverses.
  * Per application: one V-cycle (implicit.cpp LinOp::amgApply) -- on the finest level the one-level
  * preconditioner (line-implicit or block-Jacobi) as smoother, on the coarse levels forward / backward
- * colour Gauss-Seidel, on the coarsest `coarse_sweeps` of them.
+ * colour Gauss-Seidel, on the coarsest `coarse_sweeps` of them -- over the whole level (amg_smoother 0), or in
+ * the deck's bjacobi/SOR form (amg_smoother 1, mgopts.solverc:31-32): block-Jacobi between contiguous row
+ * blocks, colour Gauss-Seidel inside each, one launch per sweep (launch_amg_bjgs).
  */
 #ifndef FVHIP_AMG_HPP
 #define FVHIP_AMG_HPP
 
 #include <hip/hip_runtime.h>
+#include <map>
 #include <vector>
 #include "precond_setup.hpp"   // the host side: AmgGraph, AmgLevelHost, amgCoarsen
 
@@ -44,6 +47,13 @@ struct AmgLevel
 	int nfine = 0;                           ///< rows of the finer level
 	double *val = nullptr, *dinv = nullptr;  ///< [nnz][16], [n][16]
 	double *x = nullptr, *b = nullptr, *r = nullptr;   ///< [n][4]
+	/// the block smoother (launch_amg_bjgs): the second iterate of its ping-pong ([n][4]; x and x2 trade places
+	/// after a sweep, so the current iterate is always x), the host copy of `cells`, and per block size R the
+	/// (block, colour) offsets into `cells` (amgBlockOffsets) on the host and the device, built on first use
+	double* x2 = nullptr;
+	std::vector<int> h_cells;
+	struct BlockTable { std::vector<int> off; const int* d_off = nullptr; };
+	std::map<int, BlockTable> blocks;
 };
 
 /// val[k] = sum of the listed finer-level blocks (finest: diag / lower / upper by the AmgGraph block index
@@ -68,6 +78,15 @@ void launch_amg_gs_colour(const AmgLevel& L, int q, const double* b, double* x, 
 constexpr int AMG_BLOCK_ROWS = 2048;
 void launch_amg_gs_block(const AmgLevel& L, const double* b, double* x, int sweeps, bool fwd, bool alternate,
                          bool zero, hipStream_t s);
+constexpr int AMG_BLOCK_ROWS_DEFAULT = 256;   ///< fvhip_implicit_config::amg_block_rows = 0
+/// one sweep xout = S(xin) of block-Jacobi between contiguous row blocks of R rows (block k = rows [kR, min(n,
+/// (k+1)R)), R a multiple of 64 in [64, AMG_BLOCK_ROWS]) with colour Gauss-Seidel inside each block, a level of
+/// any size in one launch: one workgroup per block holds its rows in LDS (32 R bytes), walks the colours in
+/// direction `fwd` with a barrier after each, and reads columns outside its block from xin, which no workgroup
+/// writes (xin != xout). The row update and its summation order are those of launch_amg_gs_colour. zero: xin is
+/// taken as 0 and not read. d_off: amgBlockOffsets(.., R) on the device
+void launch_amg_bjgs(const AmgLevel& L, int R, const int* d_off, const double* b, const double* xin, double* xout,
+                     bool fwd, bool zero, hipStream_t s);
 
 }
 #endif

@@ -757,6 +757,16 @@ struct fvhip_ctx
 	int amg_levels = 0;
 	double amg_thr = -1.0;
 	void ensureAmg(int levels, double thr);
+	/// the block smoother's (block, colour) offsets of level C for blocks of R rows, on the device; built and
+	/// uploaded when R is first used on the level
+	const int* amgBlocks(AmgLevel& C, int R) {
+		AmgLevel::BlockTable& T = C.blocks[R];
+		if(!T.d_off) {
+			T.off = amgBlockOffsets(C.n, C.cstart_colour, C.h_cells, R);
+			T.d_off = upload(T.off, owned);
+		}
+		return T.d_off;
+	}
 	/// Galerkin operators of every coarse level from the finest blocks, and their diagonal inverses
 	void amgSetup(const double* diag, const double* lower, const double* upper) {
 		timed("k_amg_galerkin", [&]{

@@ -79,6 +79,7 @@ void fvhip_ctx::ensureAmg(int levels, double thr) {
 		D.val = dalloc(16*static_cast<size_t>(D.nnz), owned); D.dinv = dalloc(16*static_cast<size_t>(D.n), owned);
 		D.x = dalloc(4*static_cast<size_t>(D.n), owned); D.b = dalloc(4*static_cast<size_t>(D.n), owned);
 		D.r = dalloc(4*static_cast<size_t>(D.n), owned);
+		D.x2 = dalloc(4*static_cast<size_t>(D.n), owned); D.h_cells = H.cells;
 		amg.push_back(D);
 		g = amgGraphOf(H);
 	}
@@ -180,6 +181,31 @@ static void matfreeApply(System& S, const ArrayOf& x, const ArrayOf& y, bool hav
 	});
 }
 
+/// amg_block_rows as given (0: the default) -> the block smoother's rows per block
+static int amgBlockRows(int given)
+{
+	if(given == 0) return AMG_BLOCK_ROWS_DEFAULT;
+	if(given < 64 || given > AMG_BLOCK_ROWS || given % 64 != 0)
+		throw std::invalid_argument("amg_block_rows must be 0 (the default) or a multiple of 64 in [64, 2048]");
+	return given;
+}
+
+/// `sweeps` sweeps of the block smoother (launch_amg_bjgs, blocks of R rows) on A_C x = b, the iterate in C.x
+/// (taken as 0 if `zero`): each sweep reads C.x and writes C.x2, which then trade places, so the result is in
+/// C.x again; from zero the first sweep reads no iterate and writes C.x itself. direction: 0 forward, 1 backward,
+/// 2 alternating from forward
+static void amgBlockSweeps(fvhip_ctx* h, AmgLevel& C, int R, const double* b, int sweeps, int direction, bool zero)
+{
+	const int* off = h->amgBlocks(C, R);
+	if(zero && sweeps < 1) exact::launch_fill(C.x, 0.0, 4LL*C.n, h->stream);
+	for(int k = 0; k < sweeps; k++) {
+		const bool fwd = direction == 2 ? k % 2 == 0 : direction == 0;
+		if(zero && k == 0) { launch_amg_bjgs(C, R, off, b, C.x2, C.x, fwd, true, h->stream); continue; }
+		launch_amg_bjgs(C, R, off, b, C.x, C.x2, fwd, false, h->stream);
+		std::swap(C.x, C.x2);
+	}
+}
+
 /// The linear operator and preconditioner of one implicit step
 struct LinOp
 {
@@ -194,6 +220,7 @@ struct LinOp
 	int amg = 0;                              ///< aggregation multigrid levels (0: one-level preconditioner)
 	int amg_sweeps = 2, amg_coarse = 6, amg_fine = 2;
 	double amg_thr = 0.2;
+	int amg_smoother = 0, amg_rows = AMG_BLOCK_ROWS_DEFAULT;   ///< coarse-level smoother (cycle) and its block rows
 	std::vector<const double*> D, Lo, Up;     ///< per handle: diagonal / lower / upper blocks
 	const ArrayOf aux = [this](size_t i) { return S.hs[i]->iw.aux; };   ///< each handle's scratch vectors
 	const ArrayOf t = [this](size_t i) { return S.hs[i]->iw.t; };
@@ -331,9 +358,22 @@ struct LinOp
 		});
 	}
 	/// coarse level l of handle h's hierarchy: V-cycle on A_l x_l = b_l from x_l = 0 (colour Gauss-Seidel
-	/// forward before the coarse correction, backward after it; the coarsest level amg_coarse sweeps)
+	/// forward before the coarse correction, backward after it; the coarsest level amg_coarse sweeps,
+	/// alternating). amg_smoother 0: Gauss-Seidel over the whole level; 1: inside row blocks of amg_rows rows,
+	/// block-Jacobi between them (mgopts.solverc:31-32), same sweep counts and directions
 	void cycle(fvhip_ctx* h, size_t l) {
 		AmgLevel& C = h->amg[l];
+		if(amg_smoother == 1) {          // block-Jacobi / Gauss-Seidel: one launch per sweep on a level of any size
+			if(l + 1 == h->amg.size()) { amgBlockSweeps(h, C, amg_rows, C.b, amg_coarse, 2, true); return; }
+			amgBlockSweeps(h, C, amg_rows, C.b, amg_sweeps, 0, true);
+			launch_amg_residual(C, C.x, C.b, C.r, h->stream);
+			AmgLevel& F = h->amg[l+1];
+			launch_amg_restrict(F, C.r, F.b, h->stream);
+			cycle(h, l + 1);
+			launch_amg_prolong(F, F.x, C.x, h->stream);
+			amgBlockSweeps(h, C, amg_rows, C.b, amg_sweeps, 1, false);
+			return;
+		}
 		const bool small = C.n <= AMG_BLOCK_ROWS;        // one workgroup sweeps the level (no launch per colour)
 		if(!small) exact::launch_fill(C.x, 0.0, 4LL*C.n, h->stream);
 		const int nc = static_cast<int>(C.cstart_colour.size()) - 1;
@@ -568,6 +608,10 @@ static void checkImplicit(const fvhip_implicit_config& c)
 	if(c.prec_amg != 0 && c.prec_amg < 2) throw std::invalid_argument("prec_amg must be 0 (off) or >= 2 levels");
 	if(c.amg_sweeps < 0 || c.amg_coarse_sweeps < 0 || c.amg_fine_sweeps < 0 || !(c.amg_threshold >= 0.0 && c.amg_threshold < 1.0))
 		throw std::invalid_argument("amg_sweeps / amg_coarse_sweeps must be >= 0 and amg_threshold in [0, 1)");
+	if(c.amg_smoother != 0 && c.amg_smoother != 1)
+		throw std::invalid_argument("amg_smoother must be 0 (Gauss-Seidel over the level) or 1 (block-Jacobi / Gauss-Seidel)");
+	if(c.amg_smoother == 1 && c.prec_amg == 0) throw std::invalid_argument("amg_smoother = 1 needs prec_amg");
+	(void)amgBlockRows(c.amg_block_rows);
 	if(!(c.min_relax > 0.0)) throw std::domain_error("Minimum relaxation factor is invalid!");  // nonlinearrelaxation.cpp:20-21
 	if(c.matrix_free && !(c.mf_eps > 0.0)) throw std::invalid_argument("matrix-free difference step must be positive");
 	if(!(c.line_threshold >= 0.0) || !std::isfinite(c.line_threshold))
@@ -596,6 +640,8 @@ static void backwardEuler(System& S, const std::vector<double*>& us, const fvhip
 	A.amg_coarse = c.amg_coarse_sweeps > 0 ? c.amg_coarse_sweeps : 6;
 	A.amg_fine = c.amg_fine_sweeps > 0 ? c.amg_fine_sweeps : A.amg_sweeps;
 	A.amg_thr = c.amg_threshold > 0.0 ? c.amg_threshold : 0.2;
+	A.amg_smoother = c.amg_smoother;
+	A.amg_rows = amgBlockRows(c.amg_block_rows);
 	if(A.amg && (A.gs || A.ilu || A.sweeps != 1))
 		throw std::invalid_argument("prec_amg combines with prec_lines and prec_single only (prec_gs / prec_ilu / prec_sweeps > 1 are one-level options)");
 	for(fvhip_ctx* h : S.hs) { A.D.push_back(h->iw.jd); A.Lo.push_back(h->iw.jlo); A.Up.push_back(h->iw.jup); }
@@ -899,15 +945,26 @@ int fvhip_amg_precondition_device(fvhip_handle h, const double* d_diag, const do
                                   int levels, double threshold, int sweeps, int coarse_sweeps, double line_threshold,
                                   const double* d_v, double* d_z, int* nlevels)
 {
+	return fvhip_amg_precondition_smoother_device(h, d_diag, d_lower, d_upper, levels, threshold, sweeps, coarse_sweeps,
+	                                              line_threshold, d_v, d_z, nlevels, 0, 0);
+}
+
+int fvhip_amg_precondition_smoother_device(fvhip_handle h, const double* d_diag, const double* d_lower, const double* d_upper,
+                                           int levels, double threshold, int sweeps, int coarse_sweeps, double line_threshold,
+                                           const double* d_v, double* d_z, int* nlevels, int smoother, int block_rows)
+{
 	return guard([&] {
 		need(h, "handle");
 		need(d_diag, "diag"); if(h->L.ninface > 0) { need(d_lower, "lower"); need(d_upper, "upper"); }
 		if(levels < 2 || sweeps < 1 || coarse_sweeps < 1) throw std::invalid_argument("levels >= 2, sweeps >= 1, coarse_sweeps >= 1");
 		if((d_v == nullptr) != (d_z == nullptr)) throw std::invalid_argument("v and z go together");
+		if(smoother != 0 && smoother != 1) throw std::invalid_argument("smoother must be 0 or 1");
+		const int rows = amgBlockRows(block_rows);
 		System S = single(h);
 		h->ensureImplicit(1);
 		LinOp A{S};
 		A.amg = levels; A.amg_sweeps = A.amg_fine = sweeps; A.amg_coarse = coarse_sweeps; A.amg_thr = threshold;
+		A.amg_smoother = smoother; A.amg_rows = rows;
 		A.lines = line_threshold > 0.0; A.line_thr = line_threshold;
 		A.D = {d_diag}; A.Lo = {d_lower}; A.Up = {d_upper};
 		A.setup();
@@ -936,6 +993,69 @@ int fvhip_amg_level(fvhip_handle h, int level, int* n, int* nnz, int* agg, int* 
 		if(rowptr) HC(hipMemcpy(rowptr, L.rowptr, sizeof(int)*(static_cast<size_t>(L.n) + 1), hipMemcpyDeviceToHost));
 		if(col) HC(hipMemcpy(col, L.col, sizeof(int)*static_cast<size_t>(L.nnz), hipMemcpyDeviceToHost));
 		if(val) HC(hipMemcpy(val, L.val, 16*sizeof(double)*static_cast<size_t>(L.nnz), hipMemcpyDeviceToHost));
+	});
+}
+
+static AmgLevel& amgLevelOf(fvhip_handle h, int level)
+{
+	need(h, "handle");
+	if(level < 1 || level > static_cast<int>(h->amg.size())) throw std::invalid_argument("no such multigrid level");
+	return h->amg[static_cast<size_t>(level) - 1];
+}
+
+int fvhip_amg_smooth_level_device(fvhip_handle h, int level, int smoother, int block_rows, int sweeps, int direction,
+                                  int zero, const double* d_b, double* d_x)
+{
+	return guard([&] {
+		AmgLevel& C = amgLevelOf(h, level);
+		need(d_b, "b"); need(d_x, "x");
+		if(smoother != 0 && smoother != 1) throw std::invalid_argument("smoother must be 0 or 1");
+		if(sweeps < 1) throw std::invalid_argument("sweeps >= 1");
+		if(direction < 0 || direction > 2) throw std::invalid_argument("direction must be 0 (forward), 1 (backward) or 2 (alternating)");
+		HC(hipSetDevice(h->device));
+		const size_t bytes = 4*sizeof(double)*static_cast<size_t>(C.n);
+		if(smoother == 1) {
+			const int R = amgBlockRows(block_rows);
+			if(!zero) HC(hipMemcpyAsync(C.x, d_x, bytes, hipMemcpyDeviceToDevice, h->stream));
+			amgBlockSweeps(h, C, R, d_b, sweeps, direction, zero != 0);
+			HC(hipMemcpyAsync(d_x, C.x, bytes, hipMemcpyDeviceToDevice, h->stream));
+		} else if(C.n <= AMG_BLOCK_ROWS) {
+			launch_amg_gs_block(C, d_b, d_x, sweeps, direction == 0, direction == 2, zero != 0, h->stream);
+		} else {
+			if(zero) exact::launch_fill(d_x, 0.0, 4LL*C.n, h->stream);
+			const int nc = static_cast<int>(C.cstart_colour.size()) - 1;
+			for(int k = 0; k < sweeps; k++) {
+				const bool fwd = direction == 2 ? k % 2 == 0 : direction == 0;
+				for(int q = 0; q < nc; q++) launch_amg_gs_colour(C, fwd ? q : nc - 1 - q, d_b, d_x, h->stream);
+			}
+		}
+		HC(hipGetLastError());
+		HC(hipStreamSynchronize(h->stream));
+	});
+}
+
+int fvhip_amg_level_colours(fvhip_handle h, int level, int* ncolours, int* colour)
+{
+	return guard([&] {
+		const AmgLevel& C = amgLevelOf(h, level);
+		const int nc = static_cast<int>(C.cstart_colour.size()) - 1;
+		if(ncolours) *ncolours = nc;
+		if(colour)
+			for(int q = 0; q < nc; q++)
+				for(int k = C.cstart_colour[q]; k < C.cstart_colour[q+1]; k++) colour[C.h_cells[k]] = q;
+	});
+}
+
+int fvhip_amg_level_blocks(fvhip_handle h, int level, int block_rows, int* nblocks, int* offsets)
+{
+	return guard([&] {
+		AmgLevel& C = amgLevelOf(h, level);
+		const int R = amgBlockRows(block_rows);
+		HC(hipSetDevice(h->device));
+		h->amgBlocks(C, R);
+		const std::vector<int>& off = C.blocks[R].off;
+		if(nblocks) *nblocks = (C.n + R - 1)/R;
+		if(offsets) std::copy(off.begin(), off.end(), offsets);
 	});
 }
 

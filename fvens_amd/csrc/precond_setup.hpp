@@ -104,6 +104,11 @@ AmgGraph amgFineGraph(const CellGraph& G);
 /// aggregates graph g (threshold: strength relative to both cells' strongest coupling) and builds the
 /// coarse level: pattern, Galerkin contribution lists, member lists, colouring, coarse couplings
 AmgLevelHost amgCoarsen(const AmgGraph& g, double threshold);
+/// the block smoother's view of a level's colour order (cstart_colour / cells of amgCoarsen, n rows) cut into
+/// contiguous row blocks of R rows: off[(nb + 1) * nc], nb = ceil(n / R) blocks and nc colours; the rows of
+/// colour q in block k are cells[off[k nc + q] .. off[(k+1) nc + q]) -- a sub-range of the colour's list, which
+/// ascends (found by binary search); empty where the block has no row of the colour. R >= 1
+std::vector<int> amgBlockOffsets(int n, const std::vector<int>& cstart_colour, const std::vector<int>& cells, int R);
 /// the graph of a built coarse level (for the next aggregation)
 AmgGraph amgGraphOf(const AmgLevelHost& L);
 /// greedy colouring of a CSR adjacency in row order (a diagonal entry is skipped): the colours, and the rows

@@ -326,6 +326,12 @@ typedef struct fvhip_implicit_config {
 	double resume_res;        /*   ... its last residual norm and the one before (the CFL ramp's ratio, :462) */
 	double resume_res_prev;
 	double resume_cfl;        /*   ... and the CFL of its last step (the ramp continues from it) */
+	int amg_smoother;         /* the multigrid's smoother on its coarse levels. 0: multicolour block Gauss-Seidel over
+	                             the whole level. 1: the deck's form (mgopts.solverc:31-32, -mg_levels_pc_type bjacobi
+	                             -mg_levels_sub_pc_type sor): block-Jacobi between contiguous row blocks, Gauss-Seidel
+	                             (in colour order) inside each -- one launch per sweep whatever the level's size.
+	                             Needs prec_amg */
+	int amg_block_rows;       /* rows per block of amg_smoother 1: a multiple of 64 in [64, 2048]; 0: the default 256 */
 } fvhip_implicit_config;
 
 typedef struct fvhip_solve_stats {
@@ -374,6 +380,26 @@ int fvhip_amg_precondition_device(fvhip_handle h, const double* d_diag, const do
  *  then, where the arrays are not NULL, agg [rows of the finer level] (its aggregate), rowptr [n+1], col [nnz] and
  *  val [nnz][16] (the Galerkin blocks, row-major). Rows of level 1 aggregate the internal (Hilbert) cell order. */
 int fvhip_amg_level(fvhip_handle h, int level, int* n, int* nnz, int* agg, int* rowptr, int* col, double* val);
+/** fvhip_amg_precondition_device with the coarse levels' smoother (fvhip_implicit_config::amg_smoother) and its
+ *  rows per block (amg_block_rows; 0: the default); fvhip_amg_precondition_device is this call with (0, 0). */
+int fvhip_amg_precondition_smoother_device(fvhip_handle h, const double* d_diag, const double* d_lower, const double* d_upper,
+                                           int levels, double threshold, int sweeps, int coarse_sweeps, double line_threshold,
+                                           const double* d_v, double* d_z, int* nlevels, int smoother, int block_rows);
+/** A level smoother alone: `sweeps` (>= 1) sweeps on A_level x = b of coarse level `level` (1 = the first) of a
+ *  hierarchy built and set up by fvhip_amg_precondition[_smoother]_device. smoother 0 is what the V-cycle runs
+ *  for amg_smoother 0 (levels of at most 2048 rows in one workgroup, larger ones one launch per colour), 1 the
+ *  block smoother with `block_rows` rows per block (0: the default; ignored for smoother 0). direction: 0 all
+ *  sweeps forward in colour order, 1 all backward, 2 alternating from forward. d_b, d_x: [n][4] on the device;
+ *  d_x holds the initial guess (taken as 0, and not read, if `zero`) and receives the result. */
+int fvhip_amg_smooth_level_device(fvhip_handle h, int level, int smoother, int block_rows, int sweeps, int direction,
+                                  int zero, const double* d_b, double* d_x);
+/** The colouring of coarse level `level`: *ncolours, colour [n] (may be NULL). Rows of one colour share no block. */
+int fvhip_amg_level_colours(fvhip_handle h, int level, int* ncolours, int* colour);
+/** The block smoother's row blocks of `level` for `block_rows` rows per block (0: the default): *nblocks =
+ *  ceil(n / block_rows), and offsets [(*nblocks + 1) * ncolours] (may be NULL) into the level's rows listed colour
+ *  by colour (ascending within a colour): the rows of colour q in block k are entries offsets[k ncolours + q] ..
+ *  offsets[(k+1) ncolours + q] - 1 of that list, an empty range where the block has no row of the colour. */
+int fvhip_amg_level_blocks(fvhip_handle h, int level, int block_rows, int* nblocks, int* offsets);
 /** The colouring of the owned cells that prec_gs and prec_ilu use (greedy over interior faces in internal
  *  order): *ncolours, colour [ncell] (internal order; may be NULL), and *triples = the number of owned
  *  cells sharing faces pairwise three at a time (0: the colour-order D-ILU is exactly ILU(0)) */

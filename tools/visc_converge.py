@@ -28,7 +28,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 def run(scale=1, matrix_free=True, main_steps=400, init_steps=50, lin_maxit=60, restart=60, sweeps=3,
         tol=1e-6, heartbeat=None, cfl_init=(200.0, 1000.0), cfl_main=(500.0, 5000.0), min_relax=1.0, lin_rtol=1e-1,
         wall=None, mf_eps=None, quads=False, amg=0, amg_sweeps=2, amg_coarse=6, amg_thr=0.2, lines=True, amg_fine=0, single=False,
-        u0=None, want_state=False, chunk=0, deadline=None, symmetrize=False):
+        u0=None, want_state=False, chunk=0, deadline=None, symmetrize=False, amg_smoother=0, amg_block_rows=0):
     """the deck's two stages on the C5 mesh divided by `scale` in both directions; returns the record (a stage
     that diverges is recorded with its history and the error; the later stage is then skipped). u0: a start
     state in the mesh's cell order (mesh sequencing: a coarser member's solution carried over) -- the main
@@ -40,7 +40,8 @@ def run(scale=1, matrix_free=True, main_steps=400, init_steps=50, lin_maxit=60, 
     (exactly mirrored) hybrid mesh, u <- (u + S u)/2 with S the reflection y -> -y (rho v negated); the deck's
     flow is at alpha 0, so its steady state is symmetric, and the projection removes the antisymmetric mode that
     the unprojected pseudo-time iteration grows at the full size. The record carries the
-    antisymmetric part's norm removed by each projection"""
+    antisymmetric part's norm removed by each projection. amg_smoother / amg_block_rows: the multigrid's
+    coarse-level smoother (ImplicitConfig; 1: the deck's bjacobi/sor form) and its rows per block"""
     import torch
     import fvens_amd as fa
     import cases
@@ -68,7 +69,8 @@ def run(scale=1, matrix_free=True, main_steps=400, init_steps=50, lin_maxit=60, 
     torch.cuda.synchronize()      # torch's stream vs the library's (non-blocking) streams
     lin = dict(lin_rtol=lin_rtol, lin_maxit=lin_maxit, restart=restart, prec_lines=lines, prec_sweeps=sweeps,
                min_relax=min_relax, prec_amg=amg, amg_sweeps=amg_sweeps, amg_coarse_sweeps=amg_coarse,
-               amg_threshold=amg_thr, amg_fine_sweeps=amg_fine, prec_single=single)
+               amg_threshold=amg_thr, amg_fine_sweeps=amg_fine, prec_single=single, amg_smoother=amg_smoother,
+               amg_block_rows=amg_block_rows)
     rec = {"library": fa._ffi.build_info()["lib_src_hash"], "cells": mesh.nelem, "faces": mesh.naface, "dims": dims, "operator": "matrix-free" if matrix_free else "assembled",
            "linear": dict(lin, gmres="GMRES(%d) right-preconditioned" % restart), "cfl_init": list(cfl_init),
            "cfl_main": list(cfl_main)}
@@ -198,6 +200,9 @@ def main():
     ap.add_argument("--amg-coarse", type=int, default=6)
     ap.add_argument("--amg-thr", type=float, default=0.2)
     ap.add_argument("--amg-fine", type=int, default=0, help="finest-level sweeps (0: --amg-sweeps)")
+    ap.add_argument("--amg-smoother", type=int, default=0, help="coarse-level smoother: 0 colour Gauss-Seidel over the "
+                    "level, 1 block-Jacobi between row blocks with Gauss-Seidel inside (the deck's bjacobi/sor)")
+    ap.add_argument("--amg-block-rows", type=int, default=0, help="rows per block of --amg-smoother 1 (0: the default)")
     ap.add_argument("--single", action="store_true", help="preconditioner blocks / line factors in fp32 (prec_single)")
     ap.add_argument("--no-lines", action="store_true", help="point-block Jacobi instead of the line-implicit preconditioner")
     ap.add_argument("--sequence", type=int, nargs="+", default=None,
@@ -243,7 +248,8 @@ def main():
                       min_relax=args.min_relax, lin_rtol=args.lin_rtol, wall=args.wall, mf_eps=args.mf_eps,
                       quads=args.quads, amg=args.amg, amg_sweeps=args.amg_sweeps, amg_coarse=args.amg_coarse,
                       amg_thr=args.amg_thr, lines=not args.no_lines, amg_fine=args.amg_fine, single=args.single,
-                      chunk=args.chunk, symmetrize=args.symmetrize and sc == args.sequence[-1],
+                      amg_smoother=args.amg_smoother, amg_block_rows=args.amg_block_rows, chunk=args.chunk,
+                      symmetrize=args.symmetrize and sc == args.sequence[-1],
                       deadline=None if args.deadline is None else T0 + args.deadline)
             if sc == args.sequence[-1] and args.final_lin_rtol:
                 kw["lin_rtol"] = args.final_lin_rtol
@@ -273,7 +279,8 @@ def main():
             cfl_main=args.cfl_main, min_relax=args.min_relax, lin_rtol=args.lin_rtol, wall=args.wall, mf_eps=args.mf_eps, quads=args.quads,
             amg=args.amg, amg_sweeps=args.amg_sweeps, amg_coarse=args.amg_coarse, amg_thr=args.amg_thr,
             lines=not args.no_lines, amg_fine=args.amg_fine, single=args.single, chunk=args.chunk,
-            symmetrize=args.symmetrize, deadline=None if args.deadline is None else T0 + args.deadline)
+            amg_smoother=args.amg_smoother, amg_block_rows=args.amg_block_rows, symmetrize=args.symmetrize,
+            deadline=None if args.deadline is None else T0 + args.deadline)
     r["tag"] = args.tag
     print(json.dumps(r), flush=True)
 
