@@ -803,6 +803,19 @@ class FlowFVGroup:
     def matfree_apply_device(self, d_xs, d_ys):
         check(_ffi.lib().fvhip_group_matfree_apply_device(self._g, self._ptrs(d_xs), self._ptrs(d_ys)))
 
+    def amg_precondition_device(self, d_diags, d_lowers, d_uppers, levels=5, threshold=0.2, sweeps=2, coarse_sweeps=10,
+                                line_threshold=0.0, d_vs=None, d_zs=None, smoother=0, block_rows=0):
+        """FlowFV.amg_precondition_smoother_device over the ranks of the group (lists of one device pointer per
+        handle): every handle builds and sets up the hierarchy of its owned cells, then z = M^-1 v by one V-cycle
+        if d_vs / d_zs are given (the owned rows of each z are written; the finest residuals exchange the iterate's
+        ghost rows); returns the number of coarse levels of each handle"""
+        nl = np.zeros(len(self.sps), np.int32)
+        check(_ffi.lib().fvhip_group_amg_precondition_smoother_device(
+            self._g, self._ptrs(d_diags), self._ptrs(d_lowers), self._ptrs(d_uppers), int(levels), float(threshold),
+            int(sweeps), int(coarse_sweeps), float(line_threshold), self._ptrs(d_vs) if d_vs is not None else None,
+            self._ptrs(d_zs) if d_zs is not None else None, iptr(nl), int(smoother), int(block_rows)))
+        return [int(x) for x in nl]
+
     def close(self):
         if getattr(self, "_g", None):
             _ffi.lib().fvhip_group_destroy(self._g)

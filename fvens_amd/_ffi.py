@@ -132,6 +132,9 @@ _SIGS = {
     "fvhip_amg_precondition_smoother_device": (ctypes.c_int, [ctypes.c_void_p] * 4 + [
         ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
+    "fvhip_group_amg_precondition_smoother_device": (ctypes.c_int, [ctypes.c_void_p, _vpp, _vpp, _vpp] + [
+        ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_double, _vpp, _vpp, c_int_p, ctypes.c_int,
+        ctypes.c_int]),
     "fvhip_amg_smooth_level_device": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 6 + [ctypes.c_void_p] * 2),
     "fvhip_amg_level_colours": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_int_p, c_int_p]),
     "fvhip_amg_level_blocks": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_int_p, c_int_p]),

@@ -979,6 +979,43 @@ int fvhip_amg_precondition_smoother_device(fvhip_handle h, const double* d_diag,
 	});
 }
 
+int fvhip_group_amg_precondition_smoother_device(fvhip_group g, const double* const* d_diag, const double* const* d_lower,
+                                                 const double* const* d_upper, int levels, double threshold, int sweeps,
+                                                 int coarse_sweeps, double line_threshold, const double* const* d_v,
+                                                 double* const* d_z, int* nlevels, int smoother, int block_rows)
+{
+	return guard([&] {
+		need(g, "group");
+		const size_t n = g->hs.size();
+		needEach(d_diag, n, "diag");
+		if(!d_lower || !d_upper) throw std::invalid_argument("null argument: lower / upper");
+		for(size_t i = 0; i < n; i++) if(g->hs[i]->L.ninface > 0) { need(d_lower[i], "lower"); need(d_upper[i], "upper"); }
+		if(levels < 2 || sweeps < 1 || coarse_sweeps < 1) throw std::invalid_argument("levels >= 2, sweeps >= 1, coarse_sweeps >= 1");
+		if((d_v == nullptr) != (d_z == nullptr)) throw std::invalid_argument("v and z go together");
+		if(d_v) { needEach(d_v, n, "v"); needEach(d_z, n, "z"); }
+		if(smoother != 0 && smoother != 1) throw std::invalid_argument("smoother must be 0 or 1");
+		const int rows = amgBlockRows(block_rows);
+		System S = ofGroup(g);
+		S.each([&](size_t, fvhip_ctx* h) { h->ensureImplicit(1); });
+		LinOp A{S};
+		A.amg = levels; A.amg_sweeps = A.amg_fine = sweeps; A.amg_coarse = coarse_sweeps; A.amg_thr = threshold;
+		A.amg_smoother = smoother; A.amg_rows = rows;
+		A.lines = line_threshold > 0.0; A.line_thr = line_threshold;
+		A.D.assign(d_diag, d_diag + n); A.Lo.assign(d_lower, d_lower + n); A.Up.assign(d_upper, d_upper + n);
+		A.setup();
+		if(d_v) {
+			// z needs ghost rows for the finest residuals: each handle's own operand buffer
+			A.precondition([&](size_t i) { return const_cast<double*>(d_v[i]); }, [&](size_t i) { return S.hs[i]->iw.z; });
+			S.each([&](size_t i, fvhip_ctx* h) {
+				HC(hipMemcpyAsync(d_z[i], h->iw.z, 4*sizeof(double)*static_cast<size_t>(h->L.ncell), hipMemcpyDeviceToDevice, h->stream));
+			});
+		}
+		S.each([&](size_t, fvhip_ctx*) { HC(hipGetLastError()); });
+		S.sync();
+		if(nlevels) for(size_t i = 0; i < n; i++) nlevels[i] = static_cast<int>(S.hs[i]->amg.size());
+	});
+}
+
 int fvhip_amg_level(fvhip_handle h, int level, int* n, int* nnz, int* agg, int* rowptr, int* col, double* val)
 {
 	return guard([&] {

@@ -385,6 +385,15 @@ int fvhip_amg_level(fvhip_handle h, int level, int* n, int* nnz, int* agg, int* 
 int fvhip_amg_precondition_smoother_device(fvhip_handle h, const double* d_diag, const double* d_lower, const double* d_upper,
                                            int levels, double threshold, int sweeps, int coarse_sweeps, double line_threshold,
                                            const double* d_v, double* d_z, int* nlevels, int smoother, int block_rows);
+/** The call above for every rank of a group: each handle builds the hierarchy of its owned cells (couplings to
+ *  ghost cells are left out of the coarse operators), the finest residuals of the V-cycle take the ghost rows of
+ *  the iterate from the group's halo exchange. Arrays of one pointer per handle: d_diag / d_lower / d_upper (that
+ *  handle's blocks), d_v [ncell][4] (read on the owned rows only), d_z (the owned rows [ncell][4] are written;
+ *  both may be NULL together), nlevels [handles] (may be NULL). The same refusals as the single-handle call. */
+int fvhip_group_amg_precondition_smoother_device(fvhip_group g, const double* const* d_diag, const double* const* d_lower,
+                                                 const double* const* d_upper, int levels, double threshold, int sweeps,
+                                                 int coarse_sweeps, double line_threshold, const double* const* d_v,
+                                                 double* const* d_z, int* nlevels, int smoother, int block_rows);
 /** A level smoother alone: `sweeps` (>= 1) sweeps on A_level x = b of coarse level `level` (1 = the first) of a
  *  hierarchy built and set up by fvhip_amg_precondition[_smoother]_device. smoother 0 is what the V-cycle runs
  *  for amg_smoother 0 (levels of at most 2048 rows in one workgroup, larger ones one launch per colour), 1 the

@@ -11,7 +11,8 @@ RCCL unique id and the results; the single-GPU reference results are computed by
 
 usage (set by the test): RANK, WORLD_SIZE, MASTER_ADDR, MASTER_PORT, NCCL_HOSTID in the environment;
 argv: <out.json> <mesh key> <partitioner> [numerics]  (numerics: "visc" = laminar Roe + WLS + Van Albada +
-Sutherland, "venkat" = Roe + WLS + Venkatakrishnan)
+Sutherland, "venkat" = Roe + WLS + Venkatakrishnan; "amg" = the implicit steps preconditioned by the multigrid
+(prec_amg 3) and the rank's V-cycle against the group's, without the residual and TVD-RK legs the other rows cover)
 """
 import json
 import os
@@ -22,6 +23,60 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
+
+
+def amg_cycles(fa, torch, cases, m, p, n, part, sp, g, rank, world):
+    """the rank's V-cycle through the single-handle call (its finest residuals exchange over RCCL) against the rows
+    of this rank in the in-process group's V-cycle, on blocks both assemble themselves (CFL 20, state seed 4):
+    per case the number of owned rows whose bits differ and the largest difference relative to max|z|"""
+    def blocks(h, du, dt):
+        st = h.layout_stats()
+        Fi = max(st["faces"] - st["bfaces"], 1)
+        blk = [torch.zeros((k, 16), dtype=torch.float64, device="cuda") for k in (h.nown, Fi, Fi)]
+        torch.cuda.synchronize()
+        h.assemble_jacobian_device(du.data_ptr(), *[t.data_ptr() for t in blk])
+        h.add_pseudo_time_term_device(20.0, dt.data_ptr(), blk[0].data_ptr())
+        h.synchronize()
+        return blk
+
+    def state(h, gk):
+        du = torch.full((h.nown + h.nghost, 4), float("nan"), dtype=torch.float64, device="cuda")
+        du[:h.nown] = torch.tensor(u[gk], device="cuda")
+        return du, torch.zeros((h.nown, 4), dtype=torch.float64, device="cuda"), \
+            torch.zeros(h.nown, dtype=torch.float64, device="cuda")
+
+    u = cases.state(m, p, seed=4)
+    v = np.random.default_rng(17).standard_normal((m.nelem, 4))
+    du, dr, dt = state(sp, g)
+    torch.cuda.synchronize()
+    sp.compute_residual_device(du.data_ptr(), dr.data_ptr(), dt.data_ptr(), True, True)
+    sp.synchronize()
+    mine = blocks(sp, du, dt)
+    sps = [fa.FlowFV(m, p, n, partition=part, rank=k) for k in range(world)]
+    gs = [np.nonzero(part == k)[0][s_.permutation()] for k, s_ in enumerate(sps)]
+    sts = [state(s_, gs[k]) for k, s_ in enumerate(sps)]
+    torch.cuda.synchronize()
+    grp = fa.FlowFVGroup(sps)
+    grp.compute_residual_device(*[[t[j].data_ptr() for t in sts] for j in range(3)], True)
+    theirs = [blocks(s_, sts[k][0], sts[k][2]) for k, s_ in enumerate(sps)]
+    out = {}
+    for name, lt, smoother, rows in (("pbj_gs", 0.0, 0, 0), ("lines_bjgs64", 4.0, 1, 64)):
+        kw = dict(levels=3, threshold=0.2, sweeps=2, coarse_sweeps=6, line_threshold=lt, smoother=smoother, block_rows=rows)
+        dv, dz = torch.tensor(v[g], device="cuda"), torch.full((sp.nown, 4), float("nan"), dtype=torch.float64, device="cuda")
+        dvs = [torch.tensor(v[gk], device="cuda") for gk in gs]
+        dzs = [torch.full((s_.nown, 4), float("nan"), dtype=torch.float64, device="cuda") for s_ in sps]
+        torch.cuda.synchronize()
+        sp.amg_precondition_smoother_device(*[t.data_ptr() for t in mine], d_v=dv.data_ptr(), d_z=dz.data_ptr(), **kw)
+        grp.amg_precondition_device(*[[b[j].data_ptr() for b in theirs] for j in range(3)],
+                                    d_vs=[t.data_ptr() for t in dvs], d_zs=[t.data_ptr() for t in dzs], **kw)
+        z, zg = dz.cpu().numpy(), dzs[rank].cpu().numpy()
+        out[name] = {"finite": bool(np.isfinite(z).all() and np.isfinite(zg).all()),
+                     "rows_differing": int((z != zg).any(axis=1).sum()),
+                     "rel": float(np.abs(z - zg).max() / np.abs(zg).max())}
+    grp.close()
+    for s_ in sps:
+        s_.close()
+    return out
 
 
 def main():
@@ -43,6 +98,10 @@ def main():
     p = cases.physics("visc" if mode == "visc" else "naca")
     n = cases.numerics("ROE", "LEASTSQUARES", "VENKATAKRISHNAN" if mode == "venkat" else "VANALBADA")
     part = fa.partition_graph(m, world, weights="cost") if partitioner == "graph" else fa.partition_rcb(m, world)
+    amg = mode == "amg"
+    # before the first collective, from the partition every rank holds: a rank whose cells do not coarsen would
+    # throw inside the solve while the others wait in an allreduce
+    assert not amg or np.bincount(part, minlength=world).min() >= 128, np.bincount(part, minlength=world)
 
     def uid():
         obj = [fa.comm_unique_id() if rank == 0 else None]
@@ -67,7 +126,7 @@ def main():
     g = owned[sp.permutation()]
     p1 = one.permutation()
     bad = 0
-    for k in range(5):
+    for k in range(0 if amg else 5):
         u = cases.state(m, p, seed=20 + k)
         du1 = torch.tensor(u[p1], device="cuda")
         dr1 = torch.zeros_like(du1)
@@ -96,7 +155,8 @@ def main():
     u0 = cases.state(m, p, seed=8)
     for lines in (False, True):
         cfg = fa.ImplicitConfig(cflinit=10.0, cflfin=200.0, tol=0.0, maxiter=3, lin_rtol=1e-4, lin_maxit=60,
-                                restart=20, prec_sweeps=2 if not lines else 1, min_relax=0.2, prec_lines=lines)
+                                restart=20, prec_sweeps=2 if not (lines or amg) else 1, min_relax=0.2, prec_lines=lines,
+                                prec_amg=3 if amg else 0)
         du = torch.full((sp.nown + sp.nghost, 4), float("nan"), dtype=torch.float64, device="cuda")
         du[:sp.nown] = torch.tensor(u0[g], device="cuda")
         torch.cuda.synchronize()
@@ -126,6 +186,17 @@ def main():
                     "hist_rel": float(np.max(np.abs(np.asarray(hist) - np.asarray(histg)) / np.abs(histg))),
                     "u_rel": float(np.abs(ur - ug).max() / scale)}
         mark("implicit %s done" % key)
+
+    if amg:
+        rep["cycle"] = amg_cycles(fa, torch, cases, m, p, n, part, sp, g, rank, world)
+        mark("V-cycles done")
+        sp.close()
+        one.close()
+        with open(out_path, "w") as f:
+            json.dump(rep, f)
+        dist.barrier()
+        dist.destroy_process_group()
+        return
 
     # 3. TVD-RK: the global dtmin through ncclMin, bitwise the one-GPU steps
     mark("tvdrk")

@@ -8,7 +8,11 @@ residual norms; ncclMin of the TVD-RK time step -- checked against one GPU:
   * three implicit steps (point-block Jacobi, and the line-implicit preconditioner whose lines are cut
     at rank boundaries): the same linear iterations, residual history and states as the in-process group
     of the same partition (rounding of the dot-product sums aside: 1e-9);
-  * TVD-RK order 3: bitwise the one-GPU steps and time.
+  * TVD-RK order 3: bitwise the one-GPU steps and time;
+  * mode "amg" (3 ranks): the implicit steps preconditioned by the multigrid (prec_amg 3; point-block and line
+    finest smoother) to the same bars, and the rank's V-cycle through the single-handle call -- its finest
+    residuals exchange the iterate over RCCL -- bit for bit the rows of that rank in the in-process group's
+    V-cycle (the same kernels on the same data; measured: no row differs on any rank, either case).
 (Round 4's hipGraph capture of the rank step was removed in round 5: RCCL's captured p2p group overflows
 the stack in the HIP runtime's graph code, profiles/r05/graph_capture_crash.txt.)
 """
@@ -60,13 +64,22 @@ def _run_ranks(tmp_path, world, meshkey, partitioner, mode=""):
 
 @pytest.mark.parametrize("world,meshkey,partitioner,numerics", [(2, "naca_small", "graph", ""), (4, "naca_small", "rcb", ""),
                                                               (3, "naca_small", "graph", "visc"),
-                                                              (3, "naca_small", "graph", "venkat")])
+                                                              (3, "naca_small", "graph", "venkat"),
+                                                              (3, "naca_small", "graph", "amg")])
 def test_rccl_ranks_on_one_gpu(tmp_path, world, meshkey, partitioner, numerics):
     """the headline numerics on 2 and 4 ranks; BASELINE config 5's (laminar, Sutherland: the fused viscous
     kernel on the two-layer halo) and config 4's (Venkatakrishnan: the layer-1 ghosts' limiter values
-    formed locally) on 3 ranks"""
+    formed locally) on 3 ranks; the multigrid (config 5's preconditioner) on 3 ranks"""
     for rep in _run_ranks(tmp_path, world, meshkey, partitioner, numerics):
         assert rep["layout"]["neighbours"] > 0 and rep["layout"]["ghosts"] > 0
+        if numerics == "amg":
+            for key in ("implicit_pbj", "implicit_lines"):
+                im = rep[key]
+                assert im["steps"] == 3 and im["lin_iters"] == im["group_lin_iters"], (key, im)
+                assert im["hist_rel"] <= 1e-9 and im["u_rel"] <= 1e-9, (key, im)
+            for key in ("pbj_gs", "lines_bjgs64"):
+                assert rep["cycle"][key]["finite"] and rep["cycle"][key]["rows_differing"] == 0, (key, rep["cycle"][key])
+            continue
         assert rep["residual_mismatched_rows"] == 0, rep
         for key in ("implicit_pbj", "implicit_lines"):
             im = rep[key]
