@@ -167,6 +167,10 @@ struct fvhip_ctx
 	bool in_group = false;
 	// halo exchange overlapped with the interior patches of the fused residual (RCCL handles)
 	int* d_fz_order = nullptr;
+#ifdef FVHIP_FZ_STAMPS
+	unsigned long long* d_stamps = nullptr;   ///< probe build: the last fused launch's stamps (kernels.hip FzStamps)
+	long long stamp_blocks = 0;               ///< blocks of that launch
+#endif
 	hipStream_t comm_stream = nullptr;
 	hipEvent_t ev_u = nullptr, ev_halo = nullptr;
 	hipEvent_t ev_packed = nullptr, ev_copied = nullptr;   ///< in-process overlapped transport (groups)
@@ -336,6 +340,20 @@ struct fvhip_ctx
 		B.grad = d_grad;     // received gradients of ghost cells (partitioned meshes)
 		if(limited()) B.phi = d_phi;   // layer-1 ghosts' limiter values (two-layer halo)
 		B.mfx = mfz.x; B.mfpm = mfz.pm; B.mfres = mfz.res; B.mfmdt = mfz.mdt;
+#ifdef FVHIP_FZ_STAMPS
+		{   // one buffer for the largest launch (all patches), zeroed so that blocks without a patch read 0
+			const size_t words = 8*static_cast<size_t>(8*((M.npatch + 7)/8));
+			if(!d_stamps) {
+				void* p = nullptr;
+				HC(hipMalloc(&p, words*sizeof(unsigned long long)));
+				owned.push_back(p);
+				d_stamps = static_cast<unsigned long long*>(p);
+			}
+			HC(hipMemsetAsync(d_stamps, 0, words*sizeof(unsigned long long), st));
+			B.stamps = d_stamps;
+			stamp_blocks = 8*(((plist ? pcount : M.npatch) + 7)/8);
+		}
+#endif
 		const char* nm = nullptr;
 		timed_on(st, "k_residual_wls", [&]{ nm = KOPS(launch_residual_wls)(M, P, B, cfg.conv_numflux, recKind(), viscKind(),
 		                                                                       limKind(), dt, st); });

@@ -126,6 +126,7 @@ static fvhip_ctx* createCtx(const MeshTopo& T, const fvhip_flow_config* cfg, int
 		M.fz_gbf_start = upload(L.fz_gbf_start, o);
 		M.fz_gbf = upload(L.fz_gbf, o);
 		M.fz_cslot16 = reinterpret_cast<const uint2*>(upload(L.fz_cslot16, o));
+		M.fz_rec = upload(L.fz_rec, o);
 		M.fz_max_cells = L.fz_max_cells;
 	}
 	M.gg_n = static_cast<int>(L.gg_cells.size());
@@ -844,6 +845,25 @@ int fvhip_layout_stats(fvhip_handle h, long long* s)
 {
 	return guard([&] { need(h, "handle"); need(s, "stats"); layoutStats(h->L, s, 12); });
 }
+
+#ifdef FVHIP_FZ_STAMPS
+/// probe build only (not in include/fvhip.h; tools/fz_stamps.py): copies the stamps of the handle's last
+/// fused residual launch, eight 64-bit words per block, into out (cap words) and returns the number of
+/// blocks of that launch in *nblocks and the wall clock's rate in kHz in *wall_khz
+int fvhip_debug_fz_stamps(fvhip_ctx* h, unsigned long long* out, long long cap, long long* nblocks, int* wall_khz)
+{
+	return guard([&] {
+		if(!h || !out || !nblocks || !wall_khz) throw std::invalid_argument("null argument");
+		if(!h->d_stamps) throw std::logic_error("no fused residual has run on this handle");
+		HC(hipSetDevice(h->device));
+		HC(hipStreamSynchronize(h->stream));
+		if(cap < 8*h->stamp_blocks) throw std::invalid_argument("stamp buffer too small");
+		HC(hipMemcpy(out, h->d_stamps, 8*static_cast<size_t>(h->stamp_blocks)*sizeof(unsigned long long), hipMemcpyDeviceToHost));
+		*nblocks = h->stamp_blocks;
+		HC(hipDeviceGetAttribute(wall_khz, hipDeviceAttributeWallClockRate, h->device));
+	});
+}
+#endif
 
 int fvhip_layout_probe(const fvhip_mesh* mesh, const fvhip_flow_config* cfg, long long* s)
 {

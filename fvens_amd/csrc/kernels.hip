@@ -1193,6 +1193,33 @@ __device__ __forceinline__ void fz_viscous(const Gas& G, const double* rowi, con
 	vf[3] = e;
 }
 
+// Probe build (make EXTRA=-DFVHIP_FZ_STAMPS, into an OBJDIR and LIB of its own; tools/fz_stamps.py):
+// every wave reads the shader clock at seven points of k_residual_wls and thread 0 of each block writes
+// them at the end, with the wall-clock ticks from the first to the last, to SweepBuffers::stamps
+// (eight 64-bit words per block). The stamps stay in scalar registers until then, so no store joins
+// the loads the kernel waits for. Without the define nothing of this is compiled.
+#ifdef FVHIP_FZ_STAMPS
+struct FzStamps { unsigned long long t[7], w0; };
+#define FZ_STAMPS_PARAM , FzStamps& stamps
+#define FZ_STAMPS_ARG , stamps
+/// a stamp that what the program has issued so far in source order precedes
+#define FZ_STAMP(k) do { asm volatile("" ::: "memory"); stamps.t[k] = __builtin_amdgcn_s_memtime(); \
+                         asm volatile("" ::: "memory"); } while(0)
+/// The two stamps ahead of the patch metadata read the clock in an asm statement that is not volatile and
+/// is ordered by its inputs alone: anything with side effects there (the clock builtin included) makes the
+/// compiler load the metadata with vector instead of scalar loads, i.e. measure another kernel. The
+/// entry stamp takes the block index, the other the (uniform) values a, b, c, d it is to follow.
+#define FZ_STAMP_ENTRY() asm("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamps.t[0]) : "s"(blockIdx.x))
+#define FZ_STAMP_AFTER(k, a, b, c, d) asm("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamps.t[k]) \
+                                          : "s"(a), "s"(b), "s"(c), "s"(d))
+#else
+#define FZ_STAMPS_PARAM
+#define FZ_STAMPS_ARG
+#define FZ_STAMP(k) do {} while(0)
+#define FZ_STAMP_ENTRY() do {} while(0)
+#define FZ_STAMP_AFTER(k, a, b, c, d) do {} while(0)
+#endif
+
 /// one patch of the fused residual: uniform (scalar) metadata
 struct FzPatch { int p, s0, s1, c0, c1, nc, e0, nl, ng; const uint2* gnbr; const int* gbf; };
 /// what one thread loads for its patch before phase 0: its first staged row (state, centre), the
@@ -1200,18 +1227,21 @@ struct FzPatch { int p, s0, s1, c0, c1, nc, e0, nl, ng; const uint2* gnbr; const
 struct FzPre { int cf; double ua[4]; double2 rca; int4 nb4a; int2 lrl; double2 nn; double len;
                double2 gpa[4]; double eps2a; };     // gpa, eps2a: limited reconstructions' first-row inputs
 
+/// the patch's record (layout.hpp FzPatchRec): one uniform 32-byte load instead of three dependent
+/// rounds of scalar loads from six arrays
 __device__ __forceinline__ FzPatch fz_patch(const DevMesh& M, const SweepBuffers& B, int pi)
 {
 	FzPatch q;
 	q.p = B.plist ? B.plist[pi] : pi;
-	q.s0 = M.patch_slot[q.p]; q.s1 = M.patch_slot[q.p+1];
-	q.c0 = M.patch_cell[q.p]; q.c1 = M.patch_cell[q.p+1];
-	q.nc = q.c1 - q.c0;
-	q.e0 = M.fz_ext_start[q.p];
-	q.nl = q.nc + (M.fz_ext_start[q.p+1] - q.e0);    // staged rows: patch, ring 1, ring 2
-	q.ng = q.nc + M.fz_n1[q.p];                       // rows whose gradients the patch computes
-	q.gnbr = M.fz_gnbr16 + M.fz_g_start[q.p];
-	q.gbf = M.fz_gbf + M.fz_gbf_start[q.p];
+	const FzPatchMeta m = fz_unpack(M.fz_rec[q.p]);
+	q.s0 = m.s0; q.s1 = m.s0 + m.ns;
+	q.c0 = m.c0; q.c1 = m.c0 + m.nc;
+	q.nc = m.nc;
+	q.e0 = m.e0;
+	q.nl = m.nl;                                      // staged rows: patch, ring 1, ring 2
+	q.ng = m.ng;                                      // rows whose gradients the patch computes
+	q.gnbr = M.fz_gnbr16 + m.g0;
+	q.gbf = M.fz_gbf + m.gbf0;
 	return q;
 }
 /// a gradient row's four packed neighbour codes (layout.hpp fz_gnbr16) as patch-local index,
@@ -1222,36 +1252,73 @@ __device__ __forceinline__ int fz_nbr_code(unsigned x, const int* gbf)
 	if(x & 0x8000u) return -2 - gbf[x & 0x7FFFu];
 	return static_cast<int>(x);
 }
-__device__ __forceinline__ int4 fz_nbrs(const FzPatch& q, int i)
+__device__ __forceinline__ int4 fz_nbr_codes(uint2 v, const int* gbf)
 {
-	const uint2 v = q.gnbr[i];
-	return make_int4(fz_nbr_code(v.x & 0xFFFFu, q.gbf), fz_nbr_code(v.x >> 16, q.gbf),
-	                 fz_nbr_code(v.y & 0xFFFFu, q.gbf), fz_nbr_code(v.y >> 16, q.gbf));
+	return make_int4(fz_nbr_code(v.x & 0xFFFFu, gbf), fz_nbr_code(v.x >> 16, gbf),
+	                 fz_nbr_code(v.y & 0xFFFFu, gbf), fz_nbr_code(v.y >> 16, gbf));
 }
+__device__ __forceinline__ int4 fz_nbrs(const FzPatch& q, int i) { return fz_nbr_codes(q.gnbr[i], q.gbf); }
 __device__ __forceinline__ int fz_cell(const DevMesh& M, const FzPatch& q, int i)
 {
 	return i < q.nc ? q.c0 + i : M.fz_ext[q.e0 + (i - q.nc)];
 }
-/// the loads of FzPre (a.cf already set): the staged row and the face
-template <bool MF>
-__device__ __forceinline__ void fz_load_rows(const DevMesh& M, const SweepBuffers& B, const FzPatch& q, int t, FzPre& a)
+/// The loads of FzPre, ordered by what they depend on. Everything here needs only the patch record, except
+/// the ring rows' state and centre, which need the ring cell id: that id is requested first (the in-order
+/// vmcnt counter can then wait for it alone), and the rows are the one second-level load. The thread's
+/// own row, its face, its gradient row's neighbour codes and (limited reconstructions) its own row's face
+/// list are written without a branch, since a wait behind a divergent branch is a full one: a thread
+/// without a row, face or gradient row reads entry 0 of its patch (a patch has a cell, a cell has faces)
+/// and discards it. (gfx950, ROCm 7: the compiler folds the own and the ring row into one load of a
+/// selected cell behind a wait for the id alone, and issues the codes before it; the dependent trips
+/// before the first barrier are kernel arguments (two), record, id, rows -- profiles/r07/prologue_isa.md.)
+/// The boundary look-ups of the neighbour codes (fz_gbf) stay lazy. The codes are loaded whether or not
+/// the row's cell is owned: a ghost row holds four 0xFFFF codes (invariant of layout.cpp buildFused,
+/// checked there), which decode to the -1s it takes.
+template <bool MF, int LIM>
+__device__ __forceinline__ void fz_load_first(const DevMesh& M, const SweepBuffers& B, const FzPatch& q, int t, FzPre& a)
 {
-	a.ua[0] = a.ua[1] = a.ua[2] = a.ua[3] = 0.0;
-	a.rca = make_double2(0, 0);
-	if(t < q.nl) { ld_state<MF>(B, a.cf, a.ua); a.rca = M.rc[a.cf]; }
+	const bool own = t < q.nc, ring = !own && t < q.nl, grow = t < q.ng;
+	int cr = 0;
+	if(ring) cr = M.fz_ext[q.e0 + (t - q.nc)];
+	const int co = q.c0 + (own ? t : 0);
+	double uo[4];
+	ld_state<MF>(B, co, uo);
+	const double2 rco = M.rc[co];
 	const int s = q.s0 + t;
-	a.lrl = make_int2(0, -1); a.nn = make_double2(0, 0); a.len = 0;
-	if(s < q.s1) {
-		const unsigned v = M.fz_slot_lr16[s];    // R 0xFFFF: boundary face (bf from slot_LR)
-		a.lrl = make_int2(static_cast<int>(v & 0xFFFFu), (v >> 16) == 0xFFFFu ? -2 : static_cast<int>(v >> 16));
-		a.nn = M.slot_n[s]; a.len = M.slot_len[s];
+	const bool face = s < q.s1;
+	const int sc = face ? s : q.s0;
+	const unsigned v = M.fz_slot_lr16[sc];    // R 0xFFFF: boundary face (bf from slot_LR)
+	const double2 nn = M.slot_n[sc];
+	const double len = M.slot_len[sc];
+	const uint2 codes = q.gnbr[grow ? t : 0];
+	int4 cs = make_int4(-1, -1, -1, -1);
+	if(LIM) cs = M.cell_slots[co];
+	a.cf = own ? co : cr;
+	#pragma unroll
+	for(int k = 0; k < 4; k++) a.ua[k] = uo[k];     // (a thread without a row stages nothing)
+	a.rca = rco;
+	if(ring) {
+		ld_state<MF>(B, cr, a.ua);
+		a.rca = M.rc[cr];
+		if(LIM && grow && cr < M.nown) cs = M.cell_slots[cr];
 	}
-}
-/// the gradient inputs of the thread's first gradient row
-__device__ __forceinline__ void fz_load_grad(const DevMesh& M, const FzPatch& q, int t, FzPre& a)
-{
+	a.lrl = make_int2(0, -1); a.nn = make_double2(0, 0); a.len = 0;
+	if(face) {
+		a.lrl = make_int2(static_cast<int>(v & 0xFFFFu), (v >> 16) == 0xFFFFu ? -2 : static_cast<int>(v >> 16));
+		a.nn = nn; a.len = len;
+	}
 	a.nb4a = make_int4(-1, -1, -1, -1);
-	if(t < q.ng && a.cf < M.nown) a.nb4a = fz_nbrs(q, t);
+	if(grow) a.nb4a = fz_nbr_codes(codes, q.gbf);
+	a.eps2a = 0.0;
+	if(LIM) {   // the first row's face centres and eps^2, requested before the staging barrier
+		// (owned gradient rows only: a ghost row's limiter values come with its gradient; the other
+		// rows are left the patch's first cell's, which nothing reads)
+		const bool og = grow && a.cf < M.nown;
+		const int sl[4] = {cs.x, cs.y, cs.z, cs.w};
+		#pragma unroll
+		for(int k = 0; k < 4; k++) a.gpa[k] = sl[k] >= 0 ? M.slot_gr[sl[k] >> 1] : make_double2(0, 0);
+		if(LIM == 2) a.eps2a = M.venk_eps2[og ? a.cf : 0];
+	}
 }
 
 /// one patch (512 threads): phase 0 stages the primitive states and centres of the patch, ring-1 and
@@ -1261,7 +1328,7 @@ __device__ __forceinline__ void fz_load_grad(const DevMesh& M, const FzPatch& q,
 /// work (points at which a caller may issue loads of later work).
 template <int FLUX, int REC, bool DT, int VISC, int LIM, typename HA, typename HB>
 __device__ __forceinline__ void fz_body(const DevMesh& M, const DevPhys& P, const SweepBuffers& B, double* fz,
-                                        const FzPatch& q, const FzPre& a, HA&& hookA, HB&& hookB)
+                                        const FzPatch& q, const FzPre& a, HA&& hookA, HB&& hookB FZ_STAMPS_PARAM)
 {
 	const Gas& G = P.gas;
 	const int t = static_cast<int>(threadIdx.x);
@@ -1276,7 +1343,9 @@ __device__ __forceinline__ void fz_body(const DevMesh& M, const DevPhys& P, cons
 		ld_state<!DT>(B, c, b);
 		stage_row(G, &fz[i*W], b, M.rc[c]);
 	}
+	FZ_STAMP(2);
 	__syncthreads();
+	FZ_STAMP(3);
 
 	// phase 1: WLS gradients of the patch and ring-1 cells from the staged states
 	// (k_prep_grad_wls arithmetic, neighbours in the same ascending reference face order)
@@ -1287,6 +1356,7 @@ __device__ __forceinline__ void fz_body(const DevMesh& M, const DevPhys& P, cons
 		fused_wls_row<LIM, W, !DT>(M, P, B, fz, &fz[i*W], c, c < M.nown ? fz_nbrs(q, i) : make_int4(-1, -1, -1, -1));
 	}
 	__syncthreads();
+	FZ_STAMP(4);
 
 	// phase 2: one face per thread (k_sweep arithmetic)
 	double f[4] = {0, 0, 0, 0};
@@ -1428,6 +1498,7 @@ __device__ __forceinline__ void fz_body(const DevMesh& M, const DevPhys& P, cons
 		if(DT) { ssr[t] = sri; ssr[SLOTS_MAX + t] = srj; }
 	}
 	__syncthreads();
+	FZ_STAMP(5);
 
 	if(c < q.c1) {
 		double r[4];
@@ -1461,6 +1532,7 @@ __device__ __forceinline__ void fz_body(const DevMesh& M, const DevPhys& P, cons
 		st4(B.r, c, r);
 		if(DT) B.dtm[c] = div_rn(carea, integ);
 	}
+	FZ_STAMP(6);
 }
 
 // waves per SIMD the fused instantiations are compiled for (VGPR budgets 96 / 128 / 168); the layout
@@ -1479,24 +1551,28 @@ template <int FLUX, int REC, bool DT, int VISC, int LIM>
 __global__ void __launch_bounds__(SLOTS_MAX, VISC != SV_NONE ? FVHIP_FUSED_WAVES_VISC : (LIM ? FVHIP_FUSED_WAVES_LIM : FVHIP_FUSED_WAVES)) k_residual_wls(const DevMesh M, const DevPhys P, const SweepBuffers B)
 {
 	extern __shared__ __attribute__((aligned(16))) double fz[];
+#ifdef FVHIP_FZ_STAMPS
+	FzStamps stamps;
+	asm("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamps.w0) : "s"(blockIdx.y));
+#endif
+	FZ_STAMP_ENTRY();
 	const int np = B.plist ? B.pcount : M.npatch;
 	const int t = static_cast<int>(threadIdx.x);
 	const int q = (np + 7) >> 3;
 	const int pi = (blockIdx.x & 7) * q + (blockIdx.x >> 3);
 	if(pi >= np) return;
 	const FzPatch cur = fz_patch(M, B, pi);
+	FZ_STAMP_AFTER(1, cur.s1, cur.nl, cur.ng, cur.c0);
 	FzPre pre;
-	pre.cf = t < cur.nl ? fz_cell(M, cur, t) : 0;
-	fz_load_rows<!DT>(M, B, cur, t, pre);
-	fz_load_grad(M, cur, t, pre);
-	pre.eps2a = 0.0;
-	if(LIM) {   // the first row's face centres and eps^2, requested before the staging barrier
-		// (owned gradient rows only: a ghost row's limiter values come with its gradient)
-		const bool own = t < cur.ng && pre.cf < M.nown;
-		fz_face_centres(M, own ? pre.cf : 0, pre.gpa);
-		if(LIM == 2) pre.eps2a = M.venk_eps2[own ? pre.cf : 0];
+	fz_load_first<!DT, LIM>(M, B, cur, t, pre);
+	fz_body<FLUX, REC, DT, VISC, LIM>(M, P, B, fz, cur, pre, []() {}, []() {} FZ_STAMPS_ARG);
+#ifdef FVHIP_FZ_STAMPS
+	if(t == 0 && B.stamps) {
+		unsigned long long* o = B.stamps + 8*static_cast<size_t>(blockIdx.x);
+		for(int k = 0; k < 7; k++) o[k] = stamps.t[k];
+		o[7] = wall_clock64() - stamps.w0;
 	}
-	fz_body<FLUX, REC, DT, VISC, LIM>(M, P, B, fz, cur, pre, []() {}, []() {});
+#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1727,7 +1803,9 @@ const char* launch_residual_wls(const DevMesh& M, const DevPhys& P, const SweepB
 		}
 	}
 	const int np = B.plist ? B.pcount : M.npatch;
-	if(np > 0) hipLaunchKernelGGL(fn, dim3(8*((np + 7)/8)), dim3(SLOTS_MAX), lds, s, M, P, B);
+	// (a mesh without owned cells has one patch without cells: nothing to sweep, and the kernel's idle
+	// threads read entry 0 of their patch, which every patch of a mesh with cells has -- buildFused)
+	if(np > 0 && M.nown > 0) hipLaunchKernelGGL(fn, dim3(8*((np + 7)/8)), dim3(SLOTS_MAX), lds, s, M, P, B);
 	return kFusedNames[flux < 0 || flux > 6 ? 6 : flux];
 }
 

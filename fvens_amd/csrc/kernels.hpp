@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 #include "gasdyn.hpp"
+#include "layout.hpp"
 
 namespace fvhip {
 
@@ -50,6 +51,7 @@ struct DevMesh
 	const int* fz_gbf_start;   // [npatch+1]
 	const int* fz_gbf;         // boundary faces of the 0x8000|j codes
 	const uint2* fz_cslot16;   // [nown] 4 x 16-bit (patch-local slot << 1 | isRight)
+	const FzPatchRec* fz_rec;  // [npatch] the per-patch entries above in one 32-byte record (layout.hpp)
 	int fz_max_cells;
 	// layer-1 ghosts of a two-layer halo (layout.hpp gg_*, xb_*)
 	int gg_n;
@@ -94,6 +96,11 @@ struct SweepBuffers
 	const double* mfpm;   // [2] (|x|, eps/|x|)
 	const double* mfres;  // [N][4] -r(u) of the operator's state
 	const double* mfmdt;  // [N] pseudo-time diagonal
+#ifdef FVHIP_FZ_STAMPS
+	// probe build only (make EXTRA=-DFVHIP_FZ_STAMPS): eight 64-bit words per block of k_residual_wls,
+	// seven shader-clock stamps of its wave 0 and the wall-clock ticks from the first to the last
+	unsigned long long* stamps;
+#endif
 };
 
 // Host launchers (all asynchronous on stream). kernels.hip is compiled twice: namespace `exact`

@@ -96,8 +96,9 @@ Layout buildLayout(const MeshTopo& T, const fvhip_flow_config& cfg, bool renumbe
 	// --- patches, bounded slots and cells ---
 	// renumbered meshes: each patch is grown breadth-first over interior faces from the first
 	// unassigned cell in Hilbert order (and refilled from the next one when its region runs out), so
-	// patches are compact in the mesh graph: on C4 17.6 % ring-1 cells and 8.2 % duplicated cut faces
-	// against 35.2 % and 12.7 % for Hilbert ranges. The cells are then renumbered patch by patch
+	// patches are compact in the mesh graph: on C4 25 % ring-1 cells and 11.6 % duplicated cut faces
+	// with the 256-slot patches of this layout (512-slot patches: 17.6 % and 8.2 %, against 35.2 % and
+	// 12.7 % for Hilbert ranges of that size). The cells are then renumbered patch by patch
 	// (BFS order inside a patch). Otherwise: greedy ranges of the given order.
 	std::vector<int> mark(F, -1);
 	Lo.patch_cell.push_back(0);
@@ -559,7 +560,10 @@ void buildFused(Layout& Lo)
 		};
 		for(int i = 0; i < ng; i++) {
 			const int c = i < nc ? c0 + i : Lo.fz_ext[e0 + (i - nc)];
-			for(int j = 0; j < MAXF; j++)     // ghost cells: gradient received, no neighbour list
+			// ghost cells: gradient received, no neighbour list. All four codes -1 (0xFFFF in fz_gnbr16):
+			// k_residual_wls loads the codes of every gradient row without testing c < ncell and relies
+			// on this (checked below, where the patch records are)
+			for(int j = 0; j < MAXF; j++)
 				Lo.fz_gnbr.push_back(c < Lo.ncell ? code(Lo.cell_nbr_fo[static_cast<size_t>(c)*MAXF+j]) : -1);
 		}
 		Lo.fz_g_start.push_back(Lo.fz_g_start.back() + ng);
@@ -599,6 +603,40 @@ void buildFused(Layout& Lo)
 		innerp[p] = inner ? 1 : 0;
 		for(int c = c0; c < c1; c++) lidx[c] = -1;
 		for(size_t k = e0; k < Lo.fz_ext.size(); k++) lidx[Lo.fz_ext[k]] = -1;
+	}
+	// the per-patch entries packed into one record each (layout.hpp FzPatchRec), then decoded with the
+	// kernel's own decoder and compared with the arrays they restate
+	Lo.fz_rec.assign(npatch, FzPatchRec{});
+	for(int p = 0; p < npatch; p++) {
+		const int nc = Lo.patch_cell[p+1] - Lo.patch_cell[p], ns = Lo.patch_slot[p+1] - Lo.patch_slot[p];
+		const int n1 = Lo.fz_n1[p], nx = Lo.fz_ext_start[p+1] - Lo.fz_ext_start[p];
+		for(int v : {nc, ns, n1, nx})
+			if(v < 0 || v > 0xFFFF) throw std::logic_error("fused residual: a patch count does not fit in 16 bits");
+		// k_residual_wls lets a thread without a row, face or gradient row read entry 0 of its patch
+		if(Lo.ncell > 0 && (nc < 1 || ns < 1)) throw std::logic_error("fused residual: patch without a cell or a face");
+		FzPatchRec& r = Lo.fz_rec[p];
+		r.s0 = Lo.patch_slot[p]; r.c0 = Lo.patch_cell[p]; r.e0 = Lo.fz_ext_start[p];
+		r.g0 = Lo.fz_g_start[p]; r.gbf0 = Lo.fz_gbf_start[p];
+		r.nc_ns = static_cast<uint32_t>(nc) | (static_cast<uint32_t>(ns) << 16);
+		r.n1_nx = static_cast<uint32_t>(n1) | (static_cast<uint32_t>(nx) << 16);
+		r.spare = 0;
+	}
+	for(int p = 0; p < npatch; p++) {
+		const FzPatchMeta m = fz_unpack(Lo.fz_rec[p]);
+		const bool same = m.s0 == Lo.patch_slot[p] && m.s0 + m.ns == Lo.patch_slot[p+1]
+			&& m.c0 == Lo.patch_cell[p] && m.c0 + m.nc == Lo.patch_cell[p+1]
+			&& m.e0 == Lo.fz_ext_start[p] && m.e0 + (m.nl - m.nc) == Lo.fz_ext_start[p+1]
+			&& m.ng == m.nc + Lo.fz_n1[p] && m.g0 == Lo.fz_g_start[p] && m.g0 + m.ng == Lo.fz_g_start[p+1]
+			&& m.gbf0 == Lo.fz_gbf_start[p];
+		if(!same) throw std::logic_error("fused residual: patch record differs from the arrays it packs");
+		// the invariant k_residual_wls rests on when it loads a gradient row's codes without looking at
+		// the row's cell: a ghost row (gradient received) holds four 0xFFFF codes
+		for(int i = m.nc; i < m.ng; i++) {
+			if(Lo.fz_ext[m.e0 + (i - m.nc)] < Lo.ncell) continue;
+			const uint16_t* g = &Lo.fz_gnbr16[4*static_cast<size_t>(m.g0 + i)];
+			if(g[0] != 0xFFFF || g[1] != 0xFFFF || g[2] != 0xFFFF || g[3] != 0xFFFF)
+				throw std::logic_error("fused residual: a ghost gradient row has neighbour codes");
+		}
 	}
 	Lo.fz_order.clear();
 	for(int p = 0; p < npatch; p++) if(innerp[p]) Lo.fz_order.push_back(p);

@@ -15,8 +15,33 @@
 #include <vector>
 #include <cstdint>
 #include "../../include/fvhip.h"
+#include "gasdyn.hpp"
 
 namespace fvhip {
+
+/// One patch's metadata of the fused residual, packed for one uniform 32-byte load at the head of
+/// k_residual_wls (what patch_slot, patch_cell, fz_ext_start, fz_n1, fz_g_start and fz_gbf_start hold
+/// for the patch, which stay for the other kernels). All four counts are at most FVHIP_FUSED_ROWS.
+struct alignas(32) FzPatchRec
+{
+	int32_t s0, c0, e0, g0, gbf0;   ///< first slot, cell, fz_ext entry, fz_gnbr16 row, fz_gbf entry
+	uint32_t nc_ns;                 ///< cells | slots << 16
+	uint32_t n1_nx;                 ///< ring-1 cells | (ring-1 + ring-2 cells) << 16
+	uint32_t spare;
+};
+static_assert(sizeof(FzPatchRec) == 32, "FzPatchRec is eight 32-bit words");
+/// a record unpacked: nl staged rows (patch, ring 1, ring 2), ng rows whose gradients the patch computes
+struct FzPatchMeta { int s0, ns, c0, nc, e0, nl, ng, g0, gbf0; };
+/// the one decoder of FzPatchRec (the kernel's fz_patch and buildFused's self-check)
+FVHIP_HD FzPatchMeta fz_unpack(const FzPatchRec& r)
+{
+	FzPatchMeta m;
+	m.s0 = r.s0; m.c0 = r.c0; m.e0 = r.e0; m.g0 = r.g0; m.gbf0 = r.gbf0;
+	m.nc = static_cast<int>(r.nc_ns & 0xFFFFu); m.ns = static_cast<int>(r.nc_ns >> 16);
+	m.ng = m.nc + static_cast<int>(r.n1_nx & 0xFFFFu);
+	m.nl = m.nc + static_cast<int>(r.n1_nx >> 16);
+	return m;
+}
 
 #ifndef FVHIP_SLOTS
 #define FVHIP_SLOTS 256
@@ -110,11 +135,14 @@ struct Layout
 	// (0xFFFF none, 0x8000|j boundary face fz_gbf[fz_gbf_start[p] + j]); per owned cell its four faces
 	// as (patch-local slot << 1 | isRight), 0xFFFF padded
 	std::vector<uint32_t> fz_slot_lr16;    ///< [S]
-	std::vector<uint16_t> fz_gnbr16;       ///< [rows][4], rows as fz_gnbr
+	std::vector<uint16_t> fz_gnbr16;       ///< [rows][4], rows as fz_gnbr. Invariant the kernel relies on
+	                                       ///<  (it loads a row's codes without testing whether the row's
+	                                       ///<  cell is owned): a ghost row's four codes are all 0xFFFF
 	std::vector<int> fz_gbf_start;         ///< [npatch+1]
 	std::vector<int> fz_gbf;               ///< boundary faces the gradient rows of each patch read
 	std::vector<uint16_t> fz_cslot16;      ///< [ncell][4]
-	int fz_ring2 = 0;                      ///< ring-2 cells staged over all patches
+	std::vector<FzPatchRec> fz_rec;        ///< [npatch] the per-patch entries of the arrays above, packed
+	int fz_ring2 = 0;                     ///< ring-2 cells staged over all patches
 	int fz_max_cells = 0;
 	int fz_row_cap = 0;                    ///< fusedRowCap of the configuration
 	std::vector<int> fz_order;             ///< patches needing no halo data first (fz_ninner), then the rest
