@@ -96,6 +96,10 @@ class ImplicitConfig:
     amg_smoother: int = 0           # coarse-level smoother: 0 colour Gauss-Seidel over the level, 1 block-Jacobi between
     #                                 row blocks with Gauss-Seidel inside (-mg_levels_pc_type bjacobi -mg_levels_sub_pc_type sor)
     amg_block_rows: int = 0         # rows per block of amg_smoother 1 (multiple of 64 in [64, 2048]; 0: the default)
+    ilu_order: int = 0              # prec_ilu by fixed-point sweeps in a row order (-blasted_pc_type ilu0 / sgs): 0 the
+    #                                 colour order, 1 the internal (Hilbert) order, 2 reverse Cuthill-McKee (-mesh_reorder rcm)
+    ilu_build_sweeps: int = 0       # sweeps for the pivots (-blasted_async_sweeps b,a: b; 0: the SGS pivots)
+    ilu_apply_sweeps: int = 0       # sweeps per triangular solve (a >= 1 with an order)
 
     def _struct(self):
         c = _ffi.FvImplicitConfig()
@@ -113,6 +117,8 @@ class ImplicitConfig:
         c.amg_threshold = float(self.amg_threshold)
         c.amg_fine_sweeps = int(self.amg_fine_sweeps)
         c.amg_smoother, c.amg_block_rows = int(self.amg_smoother), int(self.amg_block_rows)
+        c.ilu_order = int(self.ilu_order)
+        c.ilu_build_sweeps, c.ilu_apply_sweeps = int(self.ilu_build_sweeps), int(self.ilu_apply_sweeps)
         if self.resume is not None:
             c.resume_res0, c.resume_res, c.resume_res_prev, c.resume_cfl = (float(x) for x in self.resume)
         return c
@@ -466,6 +472,23 @@ class FlowFV:
         """z = M^-1 v, M the block ILU(0) of the block operator in colour order (prec_ilu)"""
         check(_ffi.lib().fvhip_ilu_precondition_device(self._h, *[ctypes.c_void_p(p) for p in
                                                                   (d_diag, d_lower, d_upper, d_v, d_z)]))
+
+    def ilu_sweeps_precondition_device(self, d_diag, d_lower, d_upper, d_v, d_z, order=1, build_sweeps=0, apply_sweeps=1,
+                                       single=False):
+        """z = M^-1 v, M the sweep-based block ILU(0)/SGS in row order `order` (ImplicitConfig.ilu_order: 1 internal,
+        2 reverse Cuthill-McKee) with build_sweeps sweeps for the pivots and apply_sweeps per triangular solve;
+        single: the preconditioner's blocks in fp32"""
+        check(_ffi.lib().fvhip_ilu_sweeps_precondition_device(
+            self._h, *[ctypes.c_void_p(p) for p in (d_diag, d_lower, d_upper)], int(order), int(build_sweeps),
+            int(apply_sweeps), int(single), ctypes.c_void_p(d_v), ctypes.c_void_p(d_z)))
+
+    def ilu_order(self, order):
+        """(rank per owned cell in internal order, depth) of row order `order` of the sweep-based ILU: depth - 1
+        build sweeps give the sequential pivots, depth apply sweeps the exact triangular solves"""
+        rank = np.zeros(self.nown, np.int32)
+        depth = np.zeros(1, np.int32)
+        check(_ffi.lib().fvhip_ilu_order(self._h, int(order), iptr(rank), iptr(depth)))
+        return rank, int(depth[0])
 
     def amg_precondition_device(self, d_diag, d_lower, d_upper, levels=5, threshold=0.2, sweeps=2, coarse_sweeps=10,
                                 line_threshold=0.0, d_v=None, d_z=None):

@@ -44,7 +44,8 @@ class FvImplicitConfig(ctypes.Structure):
                 ("prec_amg", ctypes.c_int), ("amg_sweeps", ctypes.c_int), ("amg_coarse_sweeps", ctypes.c_int),
                 ("amg_threshold", ctypes.c_double), ("amg_fine_sweeps", ctypes.c_int), ("resume_res0", ctypes.c_double), ("resume_res", ctypes.c_double),
                 ("resume_res_prev", ctypes.c_double), ("resume_cfl", ctypes.c_double),
-                ("amg_smoother", ctypes.c_int), ("amg_block_rows", ctypes.c_int)]
+                ("amg_smoother", ctypes.c_int), ("amg_block_rows", ctypes.c_int),
+                ("ilu_order", ctypes.c_int), ("ilu_build_sweeps", ctypes.c_int), ("ilu_apply_sweeps", ctypes.c_int)]
 
 
 class FvSolveStats(ctypes.Structure):
@@ -125,6 +126,9 @@ _SIGS = {
     "fvhip_lines": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, c_int_p, c_int_p, c_int_p, c_int_p]),
     "fvhip_find_lines": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, c_int_p, c_int_p, c_int_p, c_int_p]),
     "fvhip_ilu_precondition_device": (ctypes.c_int, [ctypes.c_void_p] * 6),
+    "fvhip_ilu_sweeps_precondition_device": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 4 +
+                                             [ctypes.c_void_p] * 2),
+    "fvhip_ilu_order": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_int_p, c_int_p]),
     "fvhip_amg_precondition_device": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_double, ctypes.c_int,
                                                                          ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
                                                                          ctypes.c_void_p, ctypes.c_void_p]),

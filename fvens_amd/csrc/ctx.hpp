@@ -761,6 +761,29 @@ struct fvhip_ctx
 		});
 	}
 
+	/// row orders of the sweep-based block ILU(0)/SGS (fvhip_implicit_config::ilu_order 1, 2), built on first use
+	/// (precond_setup.hpp iluOrder); d_rank stays null for order 1 (the kernels compare cell indices)
+	struct IluRowOrder { bool built = false; std::vector<int> rank; int depth = 0; int* d_rank = nullptr; };
+	IluRowOrder ilu_orders[3];
+	double *ilu_dinv2 = nullptr;             ///< [ncell][16]: the factor sweeps' second buffer
+	double *ilu_p = nullptr, *ilu_q = nullptr;   ///< [ncell][4]: the solve sweeps' iterates besides the output
+	const IluRowOrder& ensureIluOrder(int order);   // implicit.cpp
+	/// the pivots of the sweep-based ILU(0) in row order `order`: dinv = (Dt^b)^-1 after b = `build` synchronous
+	/// sweeps from Dt^0 = A_ii (b = 0: the SGS pivots), the iterates alternating between dinv and ilu_dinv2 so
+	/// that the last lands in dinv
+	void iluSweepFactor(int order, int build, const double* diag, const double* lower, const double* upper, double* dinv) {
+		const IluRowOrder& O = ensureIluOrder(order);
+		const size_t N = static_cast<size_t>(L.ncell);
+		if(!ilu_dinv2) { ilu_dinv2 = dalloc(16*N, owned); ilu_p = dalloc(4*N, owned); ilu_q = dalloc(4*N, owned); }
+		auto buf = [&](int s) { return (build - s) % 2 == 0 ? dinv : ilu_dinv2; };
+		timed("k_bjac_invert", [&]{ launch_bjac_invert(L.ncell, diag, buf(0), stream); });
+		for(int s = 1; s <= build; s++)
+			timed("k_ilu_sweep_factor", [&]{
+				launch_ilu_sweep_factor(L.ncell, L.nbface, J.cell_rfaces, J.cell_nbr_fo, O.d_rank, diag, lower, upper,
+				                        buf(s - 1), buf(s), stream);
+			});
+	}
+
 	/// lines of the line-implicit preconditioner (fvhip_implicit_config::prec_lines), built on first use
 	/// from the mesh (precond_setup.hpp buildLines)
 	LineSet lines{};

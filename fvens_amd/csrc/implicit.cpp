@@ -35,6 +35,18 @@ void fvhip_ctx::ensureColouring() {
 	gs_colour = std::move(C.colour);
 }
 
+const fvhip_ctx::IluRowOrder& fvhip_ctx::ensureIluOrder(int order) {
+	if(order != 1 && order != 2) throw std::invalid_argument("ilu_order must be 1 (internal order) or 2 (reverse Cuthill-McKee)");
+	IluRowOrder& O = ilu_orders[order];
+	if(O.built) return O;
+	IluOrder H = iluOrder(cellGraph(L), order);
+	if(order == 2 && L.ncell > 0) O.d_rank = upload(H.rank, owned);
+	O.rank = std::move(H.rank);
+	O.depth = H.depth;
+	O.built = true;
+	return O;
+}
+
 void fvhip_ctx::ensureLines(double thr) {
 	if(!(thr >= 0.0) || !std::isfinite(thr)) throw std::invalid_argument("line_threshold must be finite and >= 0 (0: 4)");
 	if(thr == 0.0) thr = 4.0;
@@ -214,7 +226,9 @@ struct LinOp
 	bool single = false;                      ///< preconditioner blocks in fp32 (iw.sdinv/slo/sup; line factors: LineSet::single)
 	bool gs = false;                          ///< multicolour block Gauss-Seidel instead of Jacobi
 	bool lines = false;                       ///< line-implicit (block-tridiagonal along lines)
-	bool ilu = false;                         ///< block ILU(0) in multicolour order
+	bool ilu = false;                         ///< block ILU(0): in multicolour order, or (ilu_order) sweep-based in a row order
+	int ilu_order = 0;                        ///< 0: colour order; 1: internal order, 2: reverse Cuthill-McKee (sweep-based)
+	int ilu_build = 0, ilu_apply = 0;         ///< sweep-based form: factor sweeps (>= 0) and solve sweeps (>= 1)
 	double line_thr = 0.0;
 	int sweeps = 1;
 	int amg = 0;                              ///< aggregation multigrid levels (0: one-level preconditioner)
@@ -305,6 +319,7 @@ struct LinOp
 	/// A_ik y_k - sum_{later} A_ij z_j) = y_i - Dt_i^-1 sum_{later} A_ij z_j -- both are the Gauss-Seidel
 	/// colour kernel with the ILU pivots. Ghost rows stay zero (no exchange: block-Jacobi across ranks)
 	void iluApply(const ArrayOf& v, const ArrayOf& z) {
+		if(ilu_order) { iluSweepApply(v, z); return; }
 		S.each([&](size_t i, fvhip_ctx* h) {
 			exact::launch_fill(z(i), 0.0, 4LL*(h->L.ncell + h->L.nghost), h->stream);
 			const int nc = static_cast<int>(h->gs_colour_start.size()) - 1;
@@ -312,6 +327,35 @@ struct LinOp
 				// forward over colours 0..nc-1, backward over nc-2..0: the last colour's backward value
 				// would be its forward one again (all its neighbours are of earlier colours)
 				for(int q = 0; q < 2*nc - 1; q++) sweepColour(i, q < nc ? q : 2*nc - 2 - q, v(i), z(i));
+			});
+		});
+	}
+	/// z = M^-1 v for the sweep-based block ILU(0)/SGS in a row order (ilu_order; the reference's BLASTed
+	/// -blasted_async_sweeps b,a with init_zero, run synchronously): a = ilu_apply Jacobi-style sweeps on each
+	/// triangular system from a zero guess,
+	///     y^1 = Dt^-1 v,  y^{m+1}_i = Dt_i^-1 (v_i - sum_{lower k} A_ik y^m_k),      y = y^a,
+	///     z^1 = y,        z^{m+1}_i = y_i - Dt_i^-1 sum_{upper j} A_ij z^m_j,        z = z^a,
+	/// a forward and a - 1 backward launches over all cells, each out of place. The forward iterates alternate
+	/// between z and the handle's ilu_p so that y lands in ilu_p (in z if a = 1), the backward ones between z and
+	/// ilu_q so that the last lands in z. A fixed linear operator of v (exact once a reaches the order's depth).
+	/// Ghost neighbours are skipped and ghost rows of z are not written: block-Jacobi across ranks
+	void iluSweepApply(const ArrayOf& v, const ArrayOf& z) {
+		const int a = ilu_apply;
+		S.each([&](size_t i, fvhip_ctx* h) {
+			const int* rank = h->ensureIluOrder(ilu_order).d_rank;
+			double *p = h->ilu_p, *q = h->ilu_q, *zi = z(i);
+			auto fwd = [&](int m) { return a == 1 || (a - m) % 2 != 0 ? zi : p; };          // y^m, m = 1 .. a
+			auto bwd = [&](int m) { return m == 1 ? p : (a - m) % 2 == 0 ? zi : q; };        // z^m, m = 1 .. a
+			withBlocks(i, [&](auto B) {
+				h->timed("k_bjac_apply", [&]{ launch_bjac_apply(h->L.ncell, B.dinv, v(i), fwd(1), h->stream); });
+				for(int m = 2; m <= a; m++)
+					h->timed("k_ilu_sweep_solve", [&]{
+						launch_ilu_sweep_solve(h->J, rank, false, B.dinv, B.lo, B.up, v(i), fwd(m - 1), fwd(m), h->stream);
+					});
+				for(int m = 2; m <= a; m++)
+					h->timed("k_ilu_sweep_solve", [&]{
+						launch_ilu_sweep_solve(h->J, rank, true, B.dinv, B.lo, B.up, p, bwd(m - 1), bwd(m), h->stream);
+					});
 			});
 		});
 	}
@@ -424,7 +468,8 @@ struct LinOp
 				h->ensureLines(line_thr);
 				h->lines.single = single;
 				h->timed("k_line_factor", [&]{ launch_line_factor(h->lines, D[i], Lo[i], Up[i], h->stream); });
-			} else if(ilu) h->iluFactor(D[i], Lo[i], Up[i], w.dinv);
+			} else if(ilu && ilu_order) h->iluSweepFactor(ilu_order, ilu_build, D[i], Lo[i], Up[i], w.dinv);
+			else if(ilu) h->iluFactor(D[i], Lo[i], Up[i], w.dinv);
 			else h->timed("k_bjac_invert", [&]{ launch_bjac_invert(h->L.ncell, D[i], w.dinv, h->stream); });
 			if(gs) h->ensureColouring();
 			if(single && (amg || !lines)) {      // (the line factors are stored in fp32 by the factorisation itself)
@@ -600,8 +645,22 @@ static double expResidualRamp(double cflmin, double cflmax, double prevcfl, doub
 	else return newcfl;
 }
 
+/// the sweep-based ILU's options (fvhip_implicit_config::ilu_order / ilu_build_sweeps / ilu_apply_sweeps, and the
+/// stand-alone call's arguments); all zero: the colour-order ILU or none
+static void checkIluSweeps(int order, int build, int apply, bool prec_ilu)
+{
+	if(order < 0 || order > 2) throw std::invalid_argument("ilu_order must be 0 (colour order), 1 (internal order) or 2 (reverse Cuthill-McKee)");
+	if(build < 0) throw std::invalid_argument("ilu_build_sweeps must be >= 0");
+	if(apply < 0) throw std::invalid_argument("ilu_apply_sweeps must be >= 0");
+	if(order == 0 && build != 0) throw std::invalid_argument("ilu_build_sweeps needs ilu_order 1 or 2");
+	if(order == 0 && apply != 0) throw std::invalid_argument("ilu_apply_sweeps needs ilu_order 1 or 2");
+	if(order != 0 && !prec_ilu) throw std::invalid_argument("ilu_order needs prec_ilu");
+	if(order != 0 && apply < 1) throw std::invalid_argument("ilu_apply_sweeps must be >= 1 with ilu_order 1 or 2");
+}
+
 static void checkImplicit(const fvhip_implicit_config& c)
 {
+	checkIluSweeps(c.ilu_order, c.ilu_build_sweeps, c.ilu_apply_sweeps, c.prec_ilu != 0);
 	if(c.restart < 1 || c.restart > KRY_MAXK) throw std::invalid_argument("restart must be in [1, 128]");
 	if(c.cgs_refine < 0 || c.cgs_refine > 2) throw std::invalid_argument("cgs_refine must be 0 (never), 1 (ifneeded) or 2 (always)");
 	if(c.prec_sweeps < 1) throw std::invalid_argument("prec_sweeps must be >= 1");
@@ -633,6 +692,7 @@ static void backwardEuler(System& S, const std::vector<double*>& us, const fvhip
 	A.lines = c.prec_lines != 0;
 	A.line_thr = c.line_threshold;
 	A.ilu = c.prec_ilu != 0;
+	A.ilu_order = c.ilu_order; A.ilu_build = c.ilu_build_sweeps; A.ilu_apply = c.ilu_apply_sweeps;
 	if(A.lines && A.gs) throw std::invalid_argument("prec_lines does not combine with prec_gs");
 	if(A.ilu && (A.gs || A.lines)) throw std::invalid_argument("prec_ilu does not combine with prec_gs / prec_lines");
 	A.amg = c.prec_amg;
@@ -938,6 +998,42 @@ int fvhip_ilu_precondition_device(fvhip_handle h, const double* d_diag, const do
 		A.precondition([&](size_t) { return const_cast<double*>(d_v); }, [&](size_t) { return d_z; });
 		HC(hipGetLastError());
 		S.sync();
+	});
+}
+
+int fvhip_ilu_sweeps_precondition_device(fvhip_handle h, const double* d_diag, const double* d_lower, const double* d_upper,
+                                         int order, int build_sweeps, int apply_sweeps, int single, const double* d_v,
+                                         double* d_z)
+{
+	return guard([&] {
+		need(h, "handle");
+		need(d_diag, "diag"); if(h->L.ninface > 0) { need(d_lower, "lower"); need(d_upper, "upper"); } need(d_v, "v"); need(d_z, "z");
+		checkIluSweeps(order, build_sweeps, apply_sweeps, true);
+		if(order == 0) throw std::invalid_argument("ilu_order must be 1 (internal order) or 2 (reverse Cuthill-McKee)");
+		// ghost rows are neither read nor written (block-Jacobi across ranks), so a rank's handle needs neither its
+		// communicator nor its group here
+		System S{{h}, {}};
+		HC(hipSetDevice(h->device));
+		h->ensureImplicit(1);
+		LinOp A{S};
+		A.ilu = true; A.single = single != 0;
+		A.ilu_order = order; A.ilu_build = build_sweeps; A.ilu_apply = apply_sweeps;
+		A.D = {d_diag}; A.Lo = {d_lower}; A.Up = {d_upper};
+		A.setup();
+		A.precondition([&](size_t) { return const_cast<double*>(d_v); }, [&](size_t) { return d_z; });
+		HC(hipGetLastError());
+		S.sync();
+	});
+}
+
+int fvhip_ilu_order(fvhip_handle h, int order, int* rank, int* depth)
+{
+	return guard([&] {
+		need(h, "handle");
+		HC(hipSetDevice(h->device));
+		const fvhip_ctx::IluRowOrder& O = h->ensureIluOrder(order);
+		if(rank) std::copy(O.rank.begin(), O.rank.end(), rank);
+		if(depth) *depth = O.depth;
 	});
 }
 

@@ -522,6 +522,47 @@ void k_bjac_sweep_rows(JacMesh J, const T* __restrict__ dinv, const T* __restric
 	if(live) zout[4*static_cast<size_t>(c) + i] = o;
 }
 
+/// One sweep of a triangular solve of the sweep-based block ILU(0)/SGS (ilu_order, ilu_apply_sweeps), out of
+/// place, four lanes per cell as k_bjac_sweep_rows (row dots in face-slot order, the four sums shared within
+/// the cell's lanes, lanes past the end compute a copy and store nothing). Owned neighbour k of cell i is lower
+/// if rank[k] < rank[i], upper if rank[k] > rank[i] (rank == nullptr: the internal order); ghost neighbours
+/// are skipped (block-Jacobi across ranks).
+///   UPPER = false, the forward solve of (Dt + L) y = v:    zout_i = Dt_i^-1 (w_i - sum_{lower k} A_ik zin_k),  w = v
+///   UPPER = true, the backward solve of (I + Dt^-1 U) z = y:  zout_i = w_i - Dt_i^-1 sum_{upper j} A_ij zin_j,  w = y
+template <typename T, bool UPPER>
+__global__ __launch_bounds__(256)
+void k_ilu_sweep_solve(JacMesh J, const int* __restrict__ rank, const T* __restrict__ dinv, const T* __restrict__ lower,
+                       const T* __restrict__ upper, const double* __restrict__ w, const double* __restrict__ zin,
+                       double* __restrict__ zout)
+{
+	const long long g = static_cast<long long>(blockIdx.x)*blockDim.x + threadIdx.x;
+	const int c = static_cast<int>(g >> 2), i = static_cast<int>(g & 3);
+	const bool live = c < J.ncell;
+	const int cc = live ? c : J.ncell - 1;
+	const double4* z4 = reinterpret_cast<const double4*>(zin);
+	const double wi = w[4*static_cast<size_t>(cc) + i];
+	double acc = UPPER ? 0.0 : wi;
+	const int4 fc = J.cell_rfaces[cc];
+	const int4 nb = J.cell_nbr_fo[cc];
+	const int codes[4] = {fc.x, fc.y, fc.z, fc.w};
+	const int nbrs[4] = {nb.x, nb.y, nb.z, nb.w};
+	const int rc = rank ? rank[cc] : cc;
+#pragma unroll
+	for(int j = 0; j < 4; j++) {
+		const int code = codes[j], k = nbrs[j];
+		if(code < 0) continue;
+		const int f = code >> 1;
+		if(f < J.nbface || k < 0 || k >= J.ncell) continue;
+		const int rk = rank ? rank[k] : k;
+		if(UPPER ? rk <= rc : rk >= rc) continue;
+		const T* B = ((code & 1) ? lower : upper) + 16*static_cast<size_t>(f - J.nbface);
+		acc -= blk_row_dot(B, i, z4[k]);
+	}
+	const double4 t = make_double4(__shfl(acc, 0, 4), __shfl(acc, 1, 4), __shfl(acc, 2, 4), __shfl(acc, 3, 4));
+	const double d = blk_row_dot(dinv + 16*static_cast<size_t>(cc), i, t);
+	if(live) zout[4*static_cast<size_t>(c) + i] = UPPER ? wi + d : d;
+}
+
 /// One colour of a multicolour block Gauss-Seidel sweep, in place: z_c = D^-1 (v - sum_faces B z[nbr])
 /// for the listed cells, which share no face, so every neighbour value read is either from an
 /// earlier colour of this sweep or from the previous sweep (ghost rows: from the last exchange).
@@ -766,6 +807,22 @@ void launch_bjac_sweep(const JacMesh& J, const float* dinv, const float* lower, 
 	else
 		hipLaunchKernelGGL(k_bjac_sweep<float>, dim3(nblk(J.ncell,256)), dim3(256), 0, s, J, dinv, lower, upper, v, zin, zout);
 }
+
+template <typename T>
+static void launch_ilu_sweep_solve_t(const JacMesh& J, const int* rank, bool up, const T* dinv, const T* lower, const T* upper,
+                                     const double* w, const double* zin, double* zout, hipStream_t s)
+{
+	if(J.ncell <= 0) return;
+	const dim3 g(nblk(4LL*J.ncell,256)), b(256);
+	if(up) hipLaunchKernelGGL((k_ilu_sweep_solve<T,true>), g, b, 0, s, J, rank, dinv, lower, upper, w, zin, zout);
+	else hipLaunchKernelGGL((k_ilu_sweep_solve<T,false>), g, b, 0, s, J, rank, dinv, lower, upper, w, zin, zout);
+}
+void launch_ilu_sweep_solve(const JacMesh& J, const int* rank, bool up, const double* dinv, const double* lower,
+                            const double* upper, const double* w, const double* zin, double* zout, hipStream_t s)
+{ launch_ilu_sweep_solve_t(J, rank, up, dinv, lower, upper, w, zin, zout, s); }
+void launch_ilu_sweep_solve(const JacMesh& J, const int* rank, bool up, const float* dinv, const float* lower,
+                            const float* upper, const double* w, const double* zin, double* zout, hipStream_t s)
+{ launch_ilu_sweep_solve_t(J, rank, up, dinv, lower, upper, w, zin, zout, s); }
 
 template <typename T>
 void launch_bgs_colour_t(const JacMesh& J, const T* dinv, const T* lower, const T* upper, const double* v,

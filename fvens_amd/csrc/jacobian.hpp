@@ -47,6 +47,14 @@ void launch_bjac_sweep(const JacMesh& J, const double* dinv, const double* lower
 /// the same with fp32 blocks (fp64 vectors and arithmetic)
 void launch_bjac_sweep(const JacMesh& J, const float* dinv, const float* lower, const float* upper,
                        const double* v, const double* zin, double* zout, hipStream_t s);
+/// one sweep of a triangular solve of the sweep-based block ILU(0)/SGS in the row order `rank` (nullptr: the
+/// internal order), out of place (k_ilu_sweep_solve): up = false, zout_i = Dt_i^-1 (w_i - sum_{lower k} A_ik
+/// zin_k) with w = v; up = true, zout_i = w_i - Dt_i^-1 sum_{upper j} A_ij zin_j with w = y. dinv: the inverted
+/// pivots Dt^-1. Ghost neighbours are skipped; fp32 blocks with fp64 vectors and arithmetic in the overload
+void launch_ilu_sweep_solve(const JacMesh& J, const int* rank, bool up, const double* dinv, const double* lower,
+                            const double* upper, const double* w, const double* zin, double* zout, hipStream_t s);
+void launch_ilu_sweep_solve(const JacMesh& J, const int* rank, bool up, const float* dinv, const float* lower,
+                            const float* upper, const double* w, const double* zin, double* zout, hipStream_t s);
 /// one colour of a multicolour block Gauss-Seidel sweep, in place on z (cells: that colour's cells)
 void launch_bgs_colour(const JacMesh& J, const double* dinv, const double* lower, const double* upper,
                        const double* v, double* z, const int* cells, int n, hipStream_t s);

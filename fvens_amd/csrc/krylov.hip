@@ -90,6 +90,47 @@ void k_ilu_factor_colour(int ncell, int nbface, const int4* __restrict__ rfaces,
 	st16(dinv + 16*static_cast<size_t>(c), b);
 }
 
+/// One sweep of the fixed-point block ILU(0) in a row order (ilu_order, ilu_build_sweeps; the Chow-Patel
+/// iteration the reference reaches through BLASTed's -blasted_async_sweeps, run synchronously): for every owned
+/// cell i at once
+///     dinv_out_i = (A_ii - sum_{lower k} A_ik dinv_in_k A_ki)^-1,
+/// k lower if it is an owned neighbour across an interior face with rank[k] < rank[i] (rank == nullptr: the
+/// internal order, k < i). Reads dinv_in, writes dinv_out (another buffer): Jacobi style, so the result does
+/// not depend on the launch's schedule. k_ilu_factor_colour's arithmetic per cell
+__global__ __launch_bounds__(256)
+void k_ilu_sweep_factor(int ncell, int nbface, const int4* __restrict__ rfaces, const int4* __restrict__ nbrs,
+                        const int* __restrict__ rank, const double* __restrict__ diag, const double* __restrict__ lower,
+                        const double* __restrict__ upper, const double* __restrict__ dinv_in, double* __restrict__ dinv_out)
+{
+	const int c = blockIdx.x*blockDim.x + threadIdx.x;
+	if(c >= ncell) return;
+	double a[4][4];
+	ld16(diag + 16*static_cast<size_t>(c), a);
+	const int4 fc = rfaces[c], nb = nbrs[c];
+	const int codes[4] = {fc.x, fc.y, fc.z, fc.w};
+	const int ks[4] = {nb.x, nb.y, nb.z, nb.w};
+	const int rc = rank ? rank[c] : c;
+	for(int j = 0; j < 4; j++) {
+		const int code = codes[j], k = ks[j];
+		if(code < 0 || (code >> 1) < nbface || k < 0 || k >= ncell) continue;
+		if((rank ? rank[k] : k) >= rc) continue;
+		const size_t fi = static_cast<size_t>((code >> 1) - nbface);
+		double aik[4][4], aki[4][4], dk[4][4], tk[4][4], p[4][4];
+		ld16(((code & 1) ? lower : upper) + 16*fi, aik);
+		ld16(((code & 1) ? upper : lower) + 16*fi, aki);
+		ld16(dinv_in + 16*static_cast<size_t>(k), dk);
+		mm4(dk, aki, tk);
+		mm4(aik, tk, p);
+		#pragma unroll
+		for(int r = 0; r < 4; r++)
+			#pragma unroll
+			for(int s = 0; s < 4; s++) a[r][s] -= p[r][s];
+	}
+	double b[4][4];
+	inv4(a, b);
+	st16(dinv_out + 16*static_cast<size_t>(c), b);
+}
+
 /// y = B x for a row-major fp32 4x4 block, entries widened to fp64
 __device__ __forceinline__ void blk_mv(const float* __restrict__ B, const double4 x, double* y)
 {
@@ -803,6 +844,14 @@ void launch_ilu_factor_colour(int ncell, int nbface, const int4* rfaces, const i
 	if(n > 0) k_ilu_factor_colour<<<nblk(n,256), 256, 0, s>>>(ncell, nbface, rfaces, nbrs, colour, q, diag, lower, upper,
 	                                                           dinv, cells, n);
 }
+void launch_ilu_sweep_factor(int ncell, int nbface, const int4* rfaces, const int4* nbrs, const int* rank,
+                             const double* diag, const double* lower, const double* upper, const double* dinv_in,
+                             double* dinv_out, hipStream_t s)
+{
+	if(ncell > 0) k_ilu_sweep_factor<<<nblk(ncell,256), 256, 0, s>>>(ncell, nbface, rfaces, nbrs, rank, diag, lower, upper,
+	                                                                  dinv_in, dinv_out);
+}
+
 void launch_bjac_apply(int n, const double* dinv, const double* x, double* y, hipStream_t s)
 {
 	if(n <= 0) return;

@@ -79,6 +79,12 @@ void launch_add_rows(int n, const double* e, double* z, hipStream_t s);
 void launch_ilu_factor_colour(int ncell, int nbface, const int4* rfaces, const int4* nbrs, const int* colour, int q,
                               const double* diag, const double* lower, const double* upper, double* dinv,
                               const int* cells, int n, hipStream_t s);
+/// one synchronous sweep of the fixed-point block ILU(0) in the row order `rank` (nullptr: the internal order):
+/// dinv_out[i] = (A_ii - sum_{owned neighbours k, rank[k] < rank[i]} A_ik dinv_in[k] A_ki)^-1 for every owned
+/// cell at once (k_ilu_sweep_factor); dinv_in and dinv_out are different buffers
+void launch_ilu_sweep_factor(int ncell, int nbface, const int4* rfaces, const int4* nbrs, const int* rank,
+                             const double* diag, const double* lower, const double* upper, const double* dinv_in,
+                             double* dinv_out, hipStream_t s);
 /// dinv[c] = diag[c]^-1 (Gauss-Jordan with row pivoting), c < ncell
 void launch_bjac_invert(int ncell, const double* diag, double* dinv, hipStream_t s);
 /// y[c] = dinv[c] x[c]

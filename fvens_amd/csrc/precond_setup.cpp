@@ -55,6 +55,65 @@ Colouring colourCells(const CellGraph& G)
 	return C;
 }
 
+IluOrder iluOrder(const CellGraph& G, int order)
+{
+	if(order != 1 && order != 2) throw std::invalid_argument("ilu_order must be 1 (internal order) or 2 (reverse Cuthill-McKee)");
+	const int N = G.ncell;
+	IluOrder O;
+	O.rank.resize(static_cast<size_t>(N));
+	std::iota(O.rank.begin(), O.rank.end(), 0);
+	// owned neighbours of every cell, ascending id, and their count (the degree)
+	std::vector<std::array<int,4>> nb(static_cast<size_t>(N));
+	std::vector<int> deg(static_cast<size_t>(N), 0);
+	for(int c = 0; c < N; c++) {
+		for(const CellGraph::Nbr& b : G.nbr[c]) if(G.owned(b)) nb[c][deg[c]++] = b.cell;
+		std::sort(nb[c].begin(), nb[c].begin() + deg[c]);
+	}
+	if(order == 2) {
+		std::vector<int> dist(static_cast<size_t>(N), -1), queue, list;
+		queue.reserve(static_cast<size_t>(N)); list.reserve(static_cast<size_t>(N));
+		auto bfs = [&](int root, bool sorted) {          // fills queue with root's component; returns the last cell reached
+			queue.clear();
+			dist[root] = 0; queue.push_back(root);
+			for(size_t q = 0; q < queue.size(); q++) {
+				const int a = queue[q];
+				const size_t first = queue.size();
+				for(int j = 0; j < deg[a]; j++) {
+					const int k = nb[a][j];
+					if(dist[k] < 0) { dist[k] = dist[a] + 1; queue.push_back(k); }
+				}
+				if(sorted) std::sort(queue.begin() + first, queue.end(), [&](int x, int y) {
+					return deg[x] != deg[y] ? deg[x] < deg[y] : x < y; });
+			}
+			return queue.back();
+		};
+		std::vector<char> done(static_cast<size_t>(N), 0);
+		for(int seed = 0; seed < N; seed++) {
+			if(done[seed]) continue;
+			int root = seed;
+			for(int rep = 0; rep < 2; rep++) {           // pseudo-peripheral cell of this component
+				const int far = bfs(root, false);
+				for(const int a : queue) dist[a] = -1;
+				root = far;
+			}
+			bfs(root, true);
+			for(const int a : queue) { done[a] = 1; list.push_back(a); }
+		}
+		for(int p = 0; p < N; p++) O.rank[list[static_cast<size_t>(N - 1 - p)]] = p;
+	}
+	// longest chain of lower links: cells in rank order, each one longer than its longest lower neighbour's
+	std::vector<int> at(static_cast<size_t>(N)), len(static_cast<size_t>(N), 0);
+	for(int c = 0; c < N; c++) at[O.rank[c]] = c;
+	for(int p = 0; p < N; p++) {
+		const int c = at[p];
+		int l = 0;
+		for(int j = 0; j < deg[c]; j++) if(O.rank[nb[c][j]] < p) l = std::max(l, len[nb[c][j]]);
+		len[c] = l + 1;
+		O.depth = std::max(O.depth, len[c]);
+	}
+	return O;
+}
+
 namespace {
 
 typedef std::vector<std::pair<int,int>> Line;     ///< (cell, interior face to the previous entry; -1 at the first)

@@ -49,6 +49,22 @@ struct Colouring
 };
 Colouring colourCells(const CellGraph& G);
 
+/// A total order of the owned cells for the sweep-based ILU(0)/SGS (fvhip_implicit_config::ilu_order): owned
+/// neighbour k of cell i across an interior face is `lower` if rank[k] < rank[i], else `upper`.
+///   order 1: the internal (Hilbert) order, rank[c] = c.
+///   order 2: reverse Cuthill-McKee of the owned cells' interior-face graph (the reference's -mesh_reorder rcm):
+///     connected components in ascending lowest internal id, each started at a pseudo-peripheral cell (the
+///     farthest of the farthest of its lowest cell, partition.cpp's search), breadth-first with the unvisited
+///     neighbours taken in ascending (degree, id), the whole list reversed.
+/// depth = cells of the longest chain of lower-neighbour links: with depth - 1 build sweeps the pivots are the
+/// sequential factorisation's, with depth apply sweeps the triangular solves are exact.
+struct IluOrder
+{
+	std::vector<int> rank;                   ///< [ncell]: position of each owned cell in the order
+	int depth = 0;
+};
+IluOrder iluOrder(const CellGraph& G, int order);
+
 /// Lines of the line-implicit preconditioner. A cell is anisotropic if its strongest coupling (ghost
 /// neighbours included) is at least `thr` times its weakest; lines start at the most anisotropic unassigned
 /// cell and grow at both ends through the end cell's strongest unassigned owned neighbour while that

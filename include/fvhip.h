@@ -332,6 +332,21 @@ typedef struct fvhip_implicit_config {
 	                             (in colour order) inside each -- one launch per sweep whatever the level's size.
 	                             Needs prec_amg */
 	int amg_block_rows;       /* rows per block of amg_smoother 1: a multiple of 64 in [64, 2048]; 0: the default 256 */
+	int ilu_order;            /* prec_ilu in a row order by fixed-point sweeps (the reference's BLASTed ILU(0)/SGS,
+	                             -blasted_pc_type ilu0 / sgs with -blasted_async_sweeps b,a, -blasted_async_fact_init_type
+	                             init_sgs, -blasted_async_apply_init_type init_zero: tests/solvers/benchmark.solverc:25-35,
+	                             testcases/2dcylinder/opts.solverc:18-19; here the sweeps are synchronous, so the
+	                             preconditioner is a fixed linear operator). 0: the colour-order ILU above. 1: the
+	                             internal (Hilbert) cell order. 2: reverse Cuthill-McKee of the owned cells' face graph
+	                             (-mesh_reorder rcm). A neighbour earlier in the order is a row's lower part, a later one
+	                             its upper part; ghost neighbours are dropped (block-Jacobi across ranks). Needs prec_ilu;
+	                             prec_sweeps - 1 further residual-correction sweeps as for the colour order */
+	int ilu_build_sweeps;     /* b >= 0 sweeps over all cells for the pivots: Dt_i <- A_ii - sum_{lower k} A_ik Dt_k^-1 A_ki
+	                             from Dt = the diagonal blocks. 0: the SGS pivots (-blasted_pc_type sgs); one less than the
+	                             order's depth (fvhip_ilu_order): the sequential ILU(0) pivots. Needs ilu_order 1 or 2 */
+	int ilu_apply_sweeps;     /* a >= 1 sweeps over all cells per triangular solve, from a zero guess (a forward and a - 1
+	                             backward launches per application); a = the order's depth: the exact solves.
+	                             Needs ilu_order 1 or 2 */
 } fvhip_implicit_config;
 
 typedef struct fvhip_solve_stats {
@@ -368,6 +383,17 @@ int fvhip_line_precondition_device(fvhip_handle h, const double* d_diag, const d
  *  operator in the colour order of fvhip_colouring, then z = M^-1 v (internal order, [ncell][4]) */
 int fvhip_ilu_precondition_device(fvhip_handle h, const double* d_diag, const double* d_lower, const double* d_upper,
                                   const double* d_v, double* d_z);
+/** The sweep-based block ILU(0)/SGS preconditioner alone (fvhip_implicit_config::ilu_order, ilu_build_sweeps,
+ *  ilu_apply_sweeps; order 1 or 2): the pivots by `build_sweeps` sweeps, then z = M^-1 v by `apply_sweeps` sweeps
+ *  per triangular solve (internal order, [ncell][4]). single: the preconditioner's blocks in fp32 (prec_single).
+ *  On a rank's handle the couplings to ghost cells are dropped; only owned rows are read and written. */
+int fvhip_ilu_sweeps_precondition_device(fvhip_handle h, const double* d_diag, const double* d_lower, const double* d_upper,
+                                         int order, int build_sweeps, int apply_sweeps, int single, const double* d_v,
+                                         double* d_z);
+/** Row order `order` (1 or 2) of that preconditioner: rank [ncell] (position of each owned cell, internal ids; may be
+ *  NULL) and *depth = the cells of the longest chain of lower neighbours: depth - 1 build sweeps give the
+ *  sequential factorisation's pivots, depth apply sweeps the exact triangular solves. */
+int fvhip_ilu_order(fvhip_handle h, int order, int* rank, int* depth);
 /** The aggregation multigrid (fvhip_implicit_config::prec_amg) alone: builds the hierarchy of `levels` levels
  *  with strength threshold `threshold` (once per handle), forms the coarse Galerkin operators of the block
  *  operator (d_diag / d_lower / d_upper as in fvhip_gmres_blocks_device), then, if d_v and d_z are given,
