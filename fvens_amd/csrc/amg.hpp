@@ -18,7 +18,7 @@
  * colouring for the multicolour block Gauss-Seidel smoother.
  *
  * Per Jacobian (each pseudo-time step): the Galerkin sums level by level and the coarse diagonal inverses.
- * Per application: one V-cycle (implicit.cpp LinOp::amgApply) -- on the finest level the one-level
+ * Per application: one V-cycle (precond.cpp LinOp::amgApply) -- on the finest level the one-level
  * preconditioner (line-implicit or block-Jacobi) as smoother, on the coarse levels forward / backward
  * colour Gauss-Seidel, on the coarsest `coarse_sweeps` of them -- over the whole level (amg_smoother 0), or in
  * the deck's bjacobi/SOR form (amg_smoother 1, mgopts.solverc:31-32): block-Jacobi between contiguous row

@@ -1,7 +1,7 @@
 /** \file ctx.hpp
  * \brief The library handle (struct fvhip_ctx behind include/fvhip.h's fvhip_handle): device mesh,
  *   state scratch, residual stages with the halo exchange, Jacobian and matrix-free operator, and the
- *   work space of the implicit solver (implicit.cpp). Shared by fvhip_api.cpp and implicit.cpp.
+ *   work space of the implicit solver (implicit.cpp). Shared by fvhip_api.cpp, implicit.cpp and precond.cpp.
  * No exception crosses the ABI: entry points wrap their bodies in guard().
  */
 #ifndef FVHIP_CTX_HPP
@@ -68,6 +68,12 @@ template <typename T>
 inline void needEach(T* const* p, size_t n, const char* what) {
 	need(p, what);
 	for(size_t i = 0; i < n; i++) need(p[i], what);
+}
+
+/// the same for a call's Jacobian blocks: the diagonal, and the face blocks where the handle has interior faces
+inline void needBlocks(int ninface, const void* diag, const void* lower, const void* upper) {
+	need(diag, "diag");
+	if(ninface > 0) { need(lower, "lower"); need(upper, "upper"); }
 }
 
 template <typename T>
@@ -694,15 +700,14 @@ struct fvhip_ctx
 		iw.w = dalloc(4*N, o); iw.t = dalloc(4*N, o); iw.s = dalloc(4*N, o); iw.du = dalloc(4*N, o);
 		iw.yg = dalloc(4*N, o);
 	}
-	/// implicit-solver work space for GMRES(m): the above, the Jacobian blocks and the Krylov basis
+	/// implicit-solver work space for GMRES(m): the above, the Jacobian blocks and the Krylov basis; m in
+	/// [1, KRY_MAXK] (every caller has checked the restart length: PrecondOptions::check, fvhip_gmres_blocks_device)
 	void ensureImplicit(int m) {
 		ensureJacobian();
-		if(m < 1) throw std::invalid_argument("GMRES restart length must be positive");
 		ensureVectors();
 		const size_t N = static_cast<size_t>(L.ncell);
 		const size_t Fi = static_cast<size_t>(std::max(L.ninface, 1));
 		auto& o = owned;
-		if(m > KRY_MAXK) throw std::invalid_argument("GMRES restart length exceeds " + std::to_string(KRY_MAXK));
 		if(!iw.jd) {
 			iw.jd = dalloc(16*N, o); iw.jlo = dalloc(16*Fi, o); iw.jup = dalloc(16*Fi, o); iw.dinv = dalloc(16*N, o);
 		}
@@ -745,21 +750,10 @@ struct fvhip_ctx
 	std::vector<int> gs_colour;          ///< colour of every owned cell (also the ILU(0) order)
 	long long gs_triples = 0;            ///< owned cells sharing faces pairwise three at a time (ILU(0) fill off the diagonal)
 	int *d_gs_cells = nullptr, *d_gs_colour = nullptr;
-	void ensureColouring();                  // these three: implicit.cpp
+	void ensureColouring();                  // the preconditioner's methods, here to ensureSinglePrecond: precond.cpp
 	/// block ILU(0) factorisation in colour order (fvhip_implicit_config::prec_ilu): dinv = the inverted
 	/// pivot blocks Dt^-1, colour after colour (each colour reads the earlier colours' pivots)
-	void iluFactor(const double* diag, const double* lower, const double* upper, double* dinv, hipStream_t st = nullptr) {
-		if(!st) st = stream;
-		ensureColouring();
-		const int nc = static_cast<int>(gs_colour_start.size()) - 1;
-		timed_on(st, "k_ilu_factor", [&]{
-			for(int q = 0; q < nc; q++) {
-				const int b = gs_colour_start[q], n = gs_colour_start[q+1] - b;
-				launch_ilu_factor_colour(L.ncell, L.nbface, J.cell_rfaces, J.cell_nbr_fo, d_gs_colour, q, diag, lower, upper,
-				                         dinv, d_gs_cells + b, n, st);
-			}
-		});
-	}
+	void iluFactor(const double* diag, const double* lower, const double* upper, double* dinv, hipStream_t st = nullptr);
 
 	/// row orders of the sweep-based block ILU(0)/SGS (fvhip_implicit_config::ilu_order 1, 2), built on first use
 	/// (precond_setup.hpp iluOrder); d_rank stays null for order 1 (the kernels compare cell indices)
@@ -767,22 +761,11 @@ struct fvhip_ctx
 	IluRowOrder ilu_orders[3];
 	double *ilu_dinv2 = nullptr;             ///< [ncell][16]: the factor sweeps' second buffer
 	double *ilu_p = nullptr, *ilu_q = nullptr;   ///< [ncell][4]: the solve sweeps' iterates besides the output
-	const IluRowOrder& ensureIluOrder(int order);   // implicit.cpp
+	const IluRowOrder& ensureIluOrder(int order);
 	/// the pivots of the sweep-based ILU(0) in row order `order`: dinv = (Dt^b)^-1 after b = `build` synchronous
 	/// sweeps from Dt^0 = A_ii (b = 0: the SGS pivots), the iterates alternating between dinv and ilu_dinv2 so
 	/// that the last lands in dinv
-	void iluSweepFactor(int order, int build, const double* diag, const double* lower, const double* upper, double* dinv) {
-		const IluRowOrder& O = ensureIluOrder(order);
-		const size_t N = static_cast<size_t>(L.ncell);
-		if(!ilu_dinv2) { ilu_dinv2 = dalloc(16*N, owned); ilu_p = dalloc(4*N, owned); ilu_q = dalloc(4*N, owned); }
-		auto buf = [&](int s) { return (build - s) % 2 == 0 ? dinv : ilu_dinv2; };
-		timed("k_bjac_invert", [&]{ launch_bjac_invert(L.ncell, diag, buf(0), stream); });
-		for(int s = 1; s <= build; s++)
-			timed("k_ilu_sweep_factor", [&]{
-				launch_ilu_sweep_factor(L.ncell, L.nbface, J.cell_rfaces, J.cell_nbr_fo, O.d_rank, diag, lower, upper,
-				                        buf(s - 1), buf(s), stream);
-			});
-	}
+	void iluSweepFactor(int order, int build, const double* diag, const double* lower, const double* upper, double* dinv);
 
 	/// lines of the line-implicit preconditioner (fvhip_implicit_config::prec_lines), built on first use
 	/// from the mesh (precond_setup.hpp buildLines)
@@ -800,24 +783,9 @@ struct fvhip_ctx
 	void ensureAmg(int levels, double thr);
 	/// the block smoother's (block, colour) offsets of level C for blocks of R rows, on the device; built and
 	/// uploaded when R is first used on the level
-	const int* amgBlocks(AmgLevel& C, int R) {
-		AmgLevel::BlockTable& T = C.blocks[R];
-		if(!T.d_off) {
-			T.off = amgBlockOffsets(C.n, C.cstart_colour, C.h_cells, R);
-			T.d_off = upload(T.off, owned);
-		}
-		return T.d_off;
-	}
+	const int* amgBlocks(AmgLevel& C, int R);
 	/// Galerkin operators of every coarse level from the finest blocks, and their diagonal inverses
-	void amgSetup(const double* diag, const double* lower, const double* upper) {
-		timed("k_amg_galerkin", [&]{
-			for(size_t l = 0; l < amg.size(); l++) {
-				if(l == 0) launch_amg_galerkin_fine(amg[0], L.ncell, L.ninface, diag, lower, upper, stream);
-				else launch_amg_galerkin(amg[l], amg[l-1].val, stream);
-				launch_amg_invert(amg[l], stream);
-			}
-		});
-	}
+	void amgSetup(const double* diag, const double* lower, const double* upper);
 
 	/// frees one device array of `owned` before the handle's destruction
 	void release(const void* p) {
@@ -829,18 +797,10 @@ struct fvhip_ctx
 	}
 
 	/// fp32 copies of the preconditioner blocks (fvhip_implicit_config::prec_single)
-	void ensureSinglePrecond() {
-		if(iw.sdinv) return;
-		const size_t N = static_cast<size_t>(L.ncell);
-		const size_t Fi = static_cast<size_t>(std::max(L.ninface, 1));
-		iw.sdinv = reinterpret_cast<float*>(dalloc(8*N, owned));
-		iw.slo = reinterpret_cast<float*>(dalloc(8*Fi, owned));
-		iw.sup = reinterpret_cast<float*>(dalloc(8*Fi, owned));
-		iw.sdiag = reinterpret_cast<float*>(dalloc(8*N, owned));
-	}
+	void ensureSinglePrecond();
 
 	/// MatrixFreeSpatialJacobian::apply on device vectors (internal order), single domain (the
-	/// partitioned operator is sys_matfree, implicit.cpp)
+	/// partitioned operator is sysMatfree, implicit.cpp)
 	void matfree(const double* x, double* y) {
 		if(!mf_u || !mf_r || !mf_mdt) throw std::runtime_error("matrix-free operator: state not set");
 		if(halo()) throw std::logic_error("fvhip_ctx::matfree is the single-domain operator (partitioned: sysMatfree)");

@@ -599,7 +599,7 @@ int fvhip_assemble_jacobian_device(fvhip_handle h, const double* d_u, double* d_
 {
 	return guard([&] {
 		need(h, "handle");
-		need(d_u, "u"); need(d_diag, "diag"); if(h->L.ninface > 0) { need(d_lower, "lower"); need(d_upper, "upper"); }
+		need(d_u, "u"); needBlocks(h->L.ninface, d_diag, d_lower, d_upper);
 		HC(hipSetDevice(h->device));
 		h->assemble(d_u, d_diag, d_lower, d_upper);
 	});
@@ -622,7 +622,7 @@ int fvhip_block_apply_device(fvhip_handle h, const double* d_diag, const double*
 {
 	return guard([&] {
 		need(h, "handle");
-		need(d_diag, "diag"); if(h->L.ninface > 0) { need(d_lower, "lower"); need(d_upper, "upper"); } need(d_x, "x"); need(d_y, "y");
+		needBlocks(h->L.ninface, d_diag, d_lower, d_upper); need(d_x, "x"); need(d_y, "y");
 		HC(hipSetDevice(h->device));
 		h->ensureJacobian();
 		h->timed("k_block_apply", [&]{ launch_block_apply(h->J, d_diag, d_lower, d_upper, d_x, d_y, h->stream); });

@@ -2,7 +2,8 @@
  * \brief Host structure builders of the preconditioners (precond_setup.cpp, amg.cpp): the owned cells' graph
  *   over interior faces, the multicolour order, the lines and their 64-lane packing, the multigrid's graphs
  *   and coarse levels. Pure functions of the Layout -- no device, no handle (fvhip_ctx::ensureColouring /
- *   ensureLines / ensureAmg upload what they return) -- so they run in CPU tests.
+ *   ensureLines / ensureAmg upload what they return) -- so they run in CPU tests. The options
+ *   that select among them: precond_options.hpp.
  */
 #ifndef FVHIP_PRECOND_SETUP_HPP
 #define FVHIP_PRECOND_SETUP_HPP
