@@ -11,8 +11,6 @@
 
 namespace fvhip {
 
-static inline int nblk(long long n, int b) { return static_cast<int>((n + b - 1)/b); }
-
 __device__ __forceinline__ const double* fine_block(int src, int nfine, int nif, const double* __restrict__ diag,
                                                     const double* __restrict__ lower, const double* __restrict__ upper)
 {

@@ -1,6 +1,8 @@
 /** \file blk4.hpp
  * \brief Device helpers on row-major 4x4 fp64 blocks shared by the preconditioner kernels (krylov.hip,
  *   amg.hip): block-vector product, inverse (Gauss-Jordan with pivoting by selects), loads and stores.
+ *   Also nblk, the launch-grid size every .hip file uses (jacobian.hip and sweep_device.hpp include
+ *   this header for it: it is the one project header light enough for all of them).
  */
 #ifndef FVHIP_BLK4_HPP
 #define FVHIP_BLK4_HPP
@@ -8,6 +10,9 @@
 #include <hip/hip_runtime.h>
 
 namespace fvhip {
+
+/// blocks of b threads that cover n items: the one launch-grid helper of every .hip file
+static inline int nblk(long long n, int b) { return static_cast<int>((n + b - 1)/b); }
 
 /// y = B x for a row-major 4x4 block
 __device__ __forceinline__ void blk_mv(const double* __restrict__ B, const double4 x, double* y)

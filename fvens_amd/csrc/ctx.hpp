@@ -174,7 +174,7 @@ struct fvhip_ctx
 	// halo exchange overlapped with the interior patches of the fused residual (RCCL handles)
 	int* d_fz_order = nullptr;
 #ifdef FVHIP_FZ_STAMPS
-	unsigned long long* d_stamps = nullptr;   ///< probe build: the last fused launch's stamps (kernels.hip FzStamps)
+	unsigned long long* d_stamps = nullptr;   ///< probe build: the last fused launch's stamps (fused.hip FzStamps)
 	long long stamp_blocks = 0;               ///< blocks of that launch
 #endif
 	hipStream_t comm_stream = nullptr;

@@ -16,6 +16,7 @@
  */
 #include "jacobian.hpp"
 #include "gasjac.hpp"
+#include "blk4.hpp"      // nblk
 
 namespace fvhip {
 
@@ -714,8 +715,6 @@ void k_local_jac(gd::Gas G, int nf, const double* __restrict__ ul, const double*
 // -------------------------------------------------------------------------------------------------
 // launchers
 // -------------------------------------------------------------------------------------------------
-static inline int nblk(long long n, int b) { return static_cast<int>((n + b - 1)/b); }
-
 template <int FLUX, int VISC>
 static void jac_launch(const JacMesh& J, const DevPhys& P, const double* u, double* bblk, double* lower,
                        double* upper, hipStream_t s)

@@ -1,5 +1,5 @@
 /** \file kernels.hpp
- * \brief Launch interface of the HIP kernels of the face sweep (kernels.hip).
+ * \brief Launch interface of the HIP kernels of the face sweep (gradients.hip, sweep.hip, fused.hip).
  */
 #ifndef FVHIP_KERNELS_HPP
 #define FVHIP_KERNELS_HPP
@@ -103,9 +103,10 @@ struct SweepBuffers
 #endif
 };
 
-// Host launchers (all asynchronous on stream). kernels.hip is compiled twice: namespace `exact`
-// (-ffp-contract=off, IEEE division/sqrt: bitwise parity with the reference) and namespace `fast`
-// (contracted FMAs and approximate division/sqrt: the reference's results to a stated tolerance).
+// Host launchers (all asynchronous on stream). gradients.hip, sweep.hip and fused.hip, which define them,
+// are each compiled twice: namespace `exact` (-ffp-contract=off, IEEE division/sqrt: bitwise parity with
+// the reference) and namespace `fast` (contracted FMAs and approximate division/sqrt: the reference's
+// results to a stated tolerance).
 #define FVHIP_SWEEP_LAUNCHERS \
 void launch_prep(const DevMesh& M, const DevPhys& P, const double* u, double* up, double* ubc, double* ug, \
                  bool cells, hipStream_t s); \

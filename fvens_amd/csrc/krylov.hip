@@ -13,8 +13,6 @@ constexpr int KRY_BLOCKS = 512;   ///< partial sums of the energy norm (= ode.hi
 constexpr int KRY_DOT_BLOCKS = 2048;   ///< partial sums per GMRES dot product (8 blocks per CU: enough loads in flight)
 constexpr int KRY_GROUP = 8;      ///< dot products per block row of the multi-dot (w read once per 8 basis vectors)
 
-static inline int nblk(long long n, int b) { return static_cast<int>((n + b - 1)/b); }
-
 /// fixed-tree sum over the block of NV values per thread; thread 0 writes out[q*stride]
 template <int NV>
 __device__ __forceinline__ void block_sum(double (&acc)[NV], double* out, int stride)

@@ -496,7 +496,7 @@ void buildPipeline(Layout& Lo, int chunks)
 bool fusedEligible(const fvhip_flow_config& cfg)
 {
 	const bool limited = cfg.reconstruction == FVHIP_REC_BARTHJESPERSEN || cfg.reconstruction == FVHIP_REC_VENKATAKRISHNAN;
-	// the fused kernel inlines the common BC types' ghost states (kernels.hip ghost_c); subsonic inflow
+	// the fused kernel inlines the common BC types' ghost states (fused.hip ghost_c); subsonic inflow
 	// and isothermal walls take the staged path, whose kernels call the full ghost state out of line
 	for(int i = 0; i < cfg.nbc; i++)
 		if(cfg.bc_type[i] == FVHIP_BC_SUBSONIC_INFLOW || cfg.bc_type[i] == FVHIP_BC_ISOTHERMAL_WALL) return false;

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Where a block of the fused residual kernel spends its time: reduces the shader-clock stamps of a probe
-build of the library (kernels.hip FVHIP_FZ_STAMPS) to per-segment statistics.
+build of the library (fused.hip FVHIP_FZ_STAMPS) to per-segment statistics.
 
 Build the probe library into a directory of its own (the product library is not touched):
   make -C fvens_amd EXTRA=-DFVHIP_FZ_STAMPS OBJDIR=<dir>/obj LIB=<dir>/libfvhip_stamps.so
