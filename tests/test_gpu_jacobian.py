@@ -53,6 +53,15 @@ def test_local_flux_jacobian_bitwise(flux):
         a, b = orc.flux_jacobian(flux, gas, ul[f], ur[f], n[f])
         np.testing.assert_array_equal(dl[f], a, err_msg=f"face {f}")
         np.testing.assert_array_equal(dr[f], b, err_msg=f"face {f}")
+    # sonic subset: 200 faces on the kinks of Roe's entropy fix (Roe-averaged vn within 1e-4 c of 0, +c, -c)
+    ul, ur, n, hits = cases.sonic_faces(200)
+    assert min(hits) >= 30, hits
+    dl, dr = fa.local_flux_jacobian(flux, gas, ul, ur, n)
+    for f in range(ul.shape[0]):
+        a, b = orc.flux_jacobian(flux, gas, ul[f], ur[f], n[f])
+        assert np.all(np.isfinite(a)) and np.all(np.isfinite(b))
+        np.testing.assert_array_equal(dl[f], a, err_msg=f"sonic face {f}")
+        np.testing.assert_array_equal(dr[f], b, err_msg=f"sonic face {f}")
 
 
 def test_local_flux_jacobian_unsupported():

@@ -7,6 +7,7 @@ import pytest
 
 import fvens_amd as fa
 import cases
+import regime_cases as rcs
 from test_gpu_residual import get_mesh
 
 pytestmark = pytest.mark.gpu
@@ -26,13 +27,15 @@ CONFIGS = [("naca_small", "naca", "ROE", "LEASTSQUARES", "VANALBADA", True),
            ("naca_c2", "naca", "ROE", "LEASTSQUARES", "VENKATAKRISHNAN", True)]
 
 
-def run_partitioned(meshkey, kind, flux, grad, rec, order2, nparts, fast=False, partitioner="rcb"):
+def run_partitioned(meshkey, kind, flux, grad, rec, order2, nparts, fast=False, partitioner="rcb", state=None):
+    """kind: a cases.physics name or a FlowPhysicsConfig; state: (mesh, physics) -> cell states, by default
+    cases.state with seed 3"""
     import torch
     m, _ = get_mesh(meshkey)
-    p = cases.physics(kind)
+    p = cases.physics(kind) if isinstance(kind, str) else kind
     n = cases.numerics(flux, grad, rec, order2=order2)
     n.fast_math = fast
-    u = cases.state(m, p, seed=3)
+    u = cases.state(m, p, seed=3) if state is None else state(m, p)
     # single GPU reference
     one = fa.FlowFV(m, p, n)
     r1 = np.zeros((m.nelem, 4))
@@ -78,6 +81,22 @@ def test_partitioned_residual_bitwise(cfg, nparts):
     if cfg[1] in ("plate",) or cfg[4] == "WENO":
         # pow() paths: the same device code on both sides, so still bitwise
         pass
+    np.testing.assert_array_equal(r, r1)
+    np.testing.assert_array_equal(dt, dt1)
+
+
+@pytest.mark.parametrize("nparts", [3, 8])
+@pytest.mark.parametrize("case", rcs.PARTITION_CASES, ids=rcs.case_id)
+def test_partitioned_regime_residual_bitwise(case, nparts):
+    """cases.regime_state (supersonic faces of both signs, cells at rest, jumps, every inflow-outflow branch;
+    layout B: the subsonic-inflow ghost state) on in-process groups: every owned row bitwise one handle's.
+    test_regime_cases_host.py proves these cases finite and their branches reached."""
+    meshkey, layout, (flux, grad, rec) = case
+    seed = rcs.seeds(meshkey)[0]
+    r, dt, r1, dt1, stats = run_partitioned(meshkey, rcs.physics(layout, meshkey), flux, grad, rec, True, nparts,
+                                            state=lambda m, p: cases.regime_state(m, p, seed, rcs.JUMP))
+    assert sum(s["ghosts"] for s in stats) > 0
+    assert np.all(np.isfinite(r1)) and np.all(np.isfinite(dt1))
     np.testing.assert_array_equal(r, r1)
     np.testing.assert_array_equal(dt, dt1)
 

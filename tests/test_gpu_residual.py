@@ -231,6 +231,13 @@ def test_local_flux_bitwise(flux):
     f = fa.local_flux(flux, gas, ul, ur, nn)
     f0 = np.array([orc.flux(flux, gas, ul[i], ur[i], nn[i]) for i in range(nf)])
     np.testing.assert_array_equal(f, f0)
+    # sonic subset: 200 faces on the kinks of Roe's entropy fix (Roe-averaged vn within 1e-4 c of 0, +c, -c)
+    ul, ur, nn, hits = cases.sonic_faces(200)
+    assert min(hits) >= 30, hits           # each of the three fix lines (anumericalflux.cpp:686-692) executes
+    f = fa.local_flux(flux, gas, ul, ur, nn)
+    f0 = np.array([orc.flux(flux, gas, ul[i], ur[i], nn[i]) for i in range(ul.shape[0])])
+    assert np.all(np.isfinite(f0))
+    np.testing.assert_array_equal(f, f0)
 
 
 # ------------------------------------------------------------------------------------------------
