@@ -56,6 +56,7 @@ void* pc_build(const fvhip_mesh* mesh, const fvhip_flow_config* cfg, int nparts,
 		B->arrays[6].assign(C.cells.begin(), C.cells.begin() + L.ncell);
 		B->arrays[7] = L.if_L; B->arrays[8] = L.if_R;
 		B->arrays[9] = P.gstart; B->arrays[10] = P.cell; B->arrays[11] = P.face; B->arrays[12] = P.len;
+		B->arrays[13].assign(L.perm.begin(), L.perm.begin() + L.ncell);   // what fvhip_get_permutation hands out
 		for(size_t l = 0; l < levels.size(); l++) {
 			B->arrays[LEVEL0 + 3*l] = levels[l].agg;
 			B->arrays[LEVEL0 + 3*l + 1] = levels[l].rowptr;

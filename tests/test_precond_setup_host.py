@@ -121,19 +121,23 @@ def _lib():
 
 # arrays of the shim (pc_size / pc_copy); level l's are LEVEL0 + 3 (l - 1) + (agg, rowptr, col)
 (SCALARS, LINE_START, LINE_CELLS, LINE_FACES, COLOUR, COLOUR_START, COLOUR_CELLS, IF_L, IF_R,
- PACK_GSTART, PACK_CELL, PACK_FACE, PACK_LEN) = range(13)
+ PACK_GSTART, PACK_CELL, PACK_FACE, PACK_LEN, PERM) = range(14)
 LEVEL0 = 16
 
 
 def host_case(name):
     """the builders' output for one case: dict of int32 arrays and scalars"""
-    L = _lib()
     c = CASES[name]
-    m = c["mesh"]()
-    cfg, keep = fa._config_struct(cases.physics(c["physics"]), cases.numerics("ROE", "LEASTSQUARES", "VANALBADA"))
-    thr = c["thr"] if c["thr"] > 0 else 4.0
-    h = L.pc_build(ctypes.addressof(m.view), ctypes.addressof(cfg), c.get("nparts", 1), c.get("rank", 0), thr,
-                   AMG_LEVELS, AMG_THRESHOLD)
+    return host_structures(c["mesh"](), c["physics"], c["thr"], c.get("nparts", 1), c.get("rank", 0))
+
+
+def host_structures(m, physics, thr=0.0, nparts=1, rank=0):
+    """the builders' output for a mesh (rank `rank` of its RCB partition into nparts): dict of int32 arrays and
+    scalars; perm is what FlowFV.permutation() of such a handle returns"""
+    L = _lib()
+    cfg, keep = fa._config_struct(cases.physics(physics), cases.numerics("ROE", "LEASTSQUARES", "VANALBADA"))
+    thr = thr if thr > 0 else 4.0
+    h = L.pc_build(ctypes.addressof(m.view), ctypes.addressof(cfg), nparts, rank, thr, AMG_LEVELS, AMG_THRESHOLD)
     del keep
     assert h, L.pc_error().decode()
 
@@ -148,7 +152,8 @@ def host_case(name):
                        [int(x) for x in sc]))
         for key, what in (("start", LINE_START), ("cells", LINE_CELLS), ("faces", LINE_FACES), ("colour", COLOUR),
                           ("colour_start", COLOUR_START), ("colour_cells", COLOUR_CELLS), ("if_L", IF_L), ("if_R", IF_R),
-                          ("gstart", PACK_GSTART), ("pcell", PACK_CELL), ("pface", PACK_FACE), ("plen", PACK_LEN)):
+                          ("gstart", PACK_GSTART), ("pcell", PACK_CELL), ("pface", PACK_FACE), ("plen", PACK_LEN),
+                          ("perm", PERM)):
             out[key] = arr(what)
         out["levels"] = []
         for l in range(out["nlevels"]):
