@@ -209,6 +209,35 @@ class UMesh:
         check(_ffi.lib().fvmesh_generate(2, nx, ny, 0, xlead, height, wallspacing, ctypes.byref(h)))
         return cls(h.value)
 
+    @classmethod
+    def periodic_box(cls, nx, ny, lx=1.0, ly=1.0, triangles=False, wrap_y=False, jitter=0.0):
+        """test box on [0,lx] x [0,ly] with nx x ny cells (mesh.cpp generatePeriodicBox): markers 4 on x = 0 and
+        x = lx, 5 on both y sides if wrap_y else 2 (y = 0) and 3 (y = ly); triangles: quadrangles split with
+        alternating diagonals; jitter in [0, 0.3]: seeded displacement of the interior points. An ordinary mesh:
+        `.periodic([(4, 0)])` (and `(5, 1)` with wrap_y) makes it periodic"""
+        h = ctypes.c_void_p()
+        check(_ffi.lib().fvmesh_generate(4, int(nx), int(ny), (1 if triangles else 0) | (2 if wrap_y else 0),
+                                         float(lx), float(ly), float(jitter), ctypes.byref(h)))
+        return cls(h.value)
+
+    def periodic_map(self, marker, axis):
+        """UMesh::compute_periodic_map (mesh.cpp:369-424): per boundary face, the partner's boundary-face index
+        among the faces of `marker` (midpoints equal in the coordinate 1 - axis), -1 elsewhere"""
+        pm = np.zeros(max(self.nbface, 1), np.int32)
+        check(_ffi.lib().fvmesh_periodic_map(self._h, int(marker), int(axis), iptr(pm)))
+        return pm[:self.nbface]
+
+    def periodic(self, pairs):
+        """the mesh with the faces of each (marker, axis) of `pairs` turned into connectivity faces of the mesh
+        with itself (fvmesh_periodic): connface rows {cell, local face, -1, partner's cell, pair id}, ghost
+        centres displaced by the period. FlowFV takes the result like any mesh."""
+        pairs = list(pairs)
+        mk = np.array([p[0] for p in pairs], np.int32)
+        ax = np.array([p[1] for p in pairs], np.int32)
+        h = ctypes.c_void_p()
+        check(_ffi.lib().fvmesh_periodic(self._h, len(pairs), iptr(mk), iptr(ax), ctypes.byref(h)))
+        return UMesh(h.value)
+
     def amg_aggregates(self, threshold=0.2):
         """the aggregation multigrid's first coarsening on this mesh's cell order (host only): (aggregates, agg per cell)"""
         n = np.zeros(1, np.int32)
@@ -335,6 +364,11 @@ class FlowFV:
         """L2TraceVector::updateSharedFaces (tracevector.cpp:213-340) of this RCCL rank's per-rank mesh"""
         check(_ffi.lib().fvhip_trace_exchange_device(self._h, ctypes.c_void_p(d_left), ctypes.c_void_p(d_right),
                                                      int(width)))
+
+    def ghost_update_device(self, d_arr, width):
+        """VecGhostUpdate of a device cell array [ncell + nghost][width] (internal order, width 1..8): a gather
+        on a periodic handle, the RCCL exchange on a rank, nothing on a handle without ghost rows"""
+        check(_ffi.lib().fvhip_ghost_update_device(self._h, ctypes.c_void_p(d_arr), int(width)))
 
     # --- reference-ordered host interface -----------------------------------------------------
     def compute_residual(self, u, r, gettimesteps=False, dtm=None):

@@ -84,6 +84,7 @@ _SIGS = {
     "fvhip_build_info": (ctypes.c_char_p, []),
     "fvhip_divsqrt_probe": (ctypes.c_int, [ctypes.c_int, c_dbl_p, c_dbl_p, c_dbl_p]),
     "fvhip_trace_exchange_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
+    "fvhip_ghost_update_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
     "fvhip_group_trace_exchange_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
                                                          ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]),
     "fvhip_group_compute_residual_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
@@ -177,6 +178,8 @@ _SIGS = {
     "fvmesh_view": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(FvMeshView)]),
     "fvmesh_partition_trivial": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_int_p]),
     "fvmesh_restrict": (ctypes.c_int, [ctypes.c_void_p, c_int_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    "fvmesh_periodic_map": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_int_p]),
+    "fvmesh_periodic": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_int_p, c_int_p, ctypes.POINTER(ctypes.c_void_p)]),
     "fvmesh_global_elem_index": (ctypes.c_int, [ctypes.c_void_p, c_int_p]),
     "fvmesh_raw_info": (ctypes.c_int, [ctypes.c_void_p, c_int_p]),
     "fvmesh_raw_arrays": (ctypes.c_int, [ctypes.c_void_p, c_dbl_p, c_int_p, c_int_p, c_int_p]),

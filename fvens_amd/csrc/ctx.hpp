@@ -161,6 +161,10 @@ struct fvhip_ctx
 	// partitioned meshes: halo exchange with the neighbour ranks (RCCL, or in-process for a group)
 	int rank = 0, nparts = 1;
 	bool rankmesh = false;        ///< one rank's subdomain with connectivity faces (fvhip_create, nconnface > 0)
+	/// periodic handle: every connectivity face names rank -1, the mesh itself (makePeriodic). Rank 0 of 1; the
+	/// exchanges are gathers on the device (k_ghost_gather), no communicator or group is needed
+	bool periodic = false;
+	int* d_trace_from = nullptr;  ///< periodic handles: [nconnface] the partner's connectivity face
 	bool use_staged = false;      ///< force the staged (gradient + sweep) path even if fused applies
 	bool use_pipe = false;        ///< force the pipelined staged path even if fused applies
 	// pipelined staged residual (single domain): the sweep groups run on stream2 behind the
@@ -247,6 +251,8 @@ struct fvhip_ctx
 	}
 
 	bool halo() const { return !L.nbr_rank.empty(); }
+	/// a handle with ghost rows that nothing fills yet: partitioned, without its communicator
+	bool needsComm() const { return halo() && !comm && !periodic; }
 	int ntotal() const { return L.ncell + L.nghost; }
 
 	// --- residual stages (FlowFV::compute_residual, flow_spatial.cpp:636-816); between them the
@@ -415,6 +421,13 @@ struct fvhip_ctx
 		timed_on(st, "k_unpack", [&]{ launch_unpack_rows(d_trace_conn, L.nghost, d_tracebuf, width, right, st); });
 	}
 	void trace_exchange_rccl(const double* left, double* right, int width) {
+		if(periodic) {        // right[ic] = left[partner(ic)] in one launch
+			if(width < 1 || width > 4) throw std::invalid_argument("face-trace exchange: width must be 1..4");
+			if(left == right) throw std::invalid_argument("face-trace exchange: left and right must be different arrays");
+			timed("k_ghost_gather", [&]{ launch_ghost_gather(d_trace_from, L.nghost, left, width, right, 0, stream); });
+			HC(hipGetLastError());
+			return;
+		}
 		if(!comm) throw std::runtime_error("face-trace exchange: call fvhip_comm_init (or use a group) first");
 		trace_pack(left, width, stream);
 		NC(ncclGroupStart());
@@ -434,8 +447,14 @@ struct fvhip_ctx
 	/// with nothing to move is skipped on both.
 	void exchange_rccl(double* arr, int width, hipStream_t st = nullptr, int layers = 1) {
 		if(!halo()) return;
-		if(!comm) throw std::runtime_error("partitioned handle: call fvhip_comm_init (or use a group) first");
 		if(!st) st = stream;
+		if(periodic) {        // ghost row g = the row of the partner cell d_send[g]: one launch, no buffer
+			if(width < 1 || width > 8) throw std::invalid_argument("ghost exchange: width must be 1..8");
+			timed_on(st, "k_ghost_gather", [&]{ launch_ghost_gather(d_send, L.nghost, arr, width, arr, L.ncell, st); });
+			HC(hipGetLastError());
+			return;
+		}
+		if(!comm) throw std::runtime_error("partitioned handle: call fvhip_comm_init (or use a group) first");
 		pack(arr, width, st);
 		NC(ncclGroupStart());
 		for(size_t k = 0; k < L.nbr_rank.size(); k++) {

@@ -185,9 +185,17 @@ int fvhip_create(const fvhip_mesh* mesh, const fvhip_flow_config* cfg, int devic
 		if(!mesh || !cfg || !out) throw std::invalid_argument("null argument");
 		if(mesh->nconnface > 0) {
 			// one rank's subdomain: its rank comes with the communicator (or fvhip_set_rank)
-			fvhip_ctx* h = createCtx(topoFromRankMesh(*mesh), cfg, device);
+			std::unique_ptr<fvhip_ctx> h(createCtx(topoFromRankMesh(*mesh), cfg, device));
 			h->rankmesh = true; h->rank = -1; h->nparts = 0;
-			*out = h;
+			if(h->L.nbr_rank.size() == 1 && h->L.nbr_rank[0] == -1) {
+				// a periodic mesh: rank 0 of 1, the exchanges are gathers on the device (k_ghost_gather)
+				h->periodic = true; h->rank = 0; h->nparts = 1;
+				const int nc = h->L.nghost;
+				std::vector<int> from(nc);      // ghosts 2j and 2j+1 are the two sides of pair j (topoFromRankMesh)
+				for(int g = 0; g < nc; g++) from[h->L.trace_conn[g]] = h->L.trace_conn[g ^ 1];
+				h->d_trace_from = upload(from, h->owned);
+			}
+			*out = h.release();
 			return;
 		}
 		*out = createCtx(topoFromMesh(*mesh), cfg, device);
@@ -198,6 +206,7 @@ int fvhip_set_rank(fvhip_handle h, int rank, int nranks)
 {
 	return guard([&] {
 		need(h, "handle");
+		if(h->periodic) throw std::invalid_argument("fvhip_set_rank: a periodic handle is rank 0 of 1 and takes no rank");
 		if(!h->rankmesh) throw std::invalid_argument("fvhip_set_rank: not a per-rank mesh handle");
 		if(rank < 0 || rank >= nranks) throw std::invalid_argument("rank out of range");
 		for(int q : h->L.nbr_rank)
@@ -242,6 +251,7 @@ int fvhip_partition_rcb(const fvhip_mesh* mesh, int nparts, int* part)
 {
 	return guard([&] {
 		need(mesh, "mesh"); need(part, "part");
+		if(mesh->nconnface != 0) throw std::invalid_argument("partitionRCB: expects the single-domain mesh");
 		const std::vector<int> p = partitionRCB(mesh->rc, mesh->nelem, nparts);
 		std::memcpy(part, p.data(), p.size()*sizeof(int));
 	});
@@ -315,6 +325,7 @@ int fvhip_comm_init(fvhip_handle h, int nranks, int rank, const void* id128)
 {
 	return guard([&] {
 		need(h, "handle"); need(id128, "unique id");
+		if(h->periodic) throw std::invalid_argument("fvhip_comm_init: a periodic handle exchanges on its own device and takes no communicator");
 		if(h->rankmesh && h->rank < 0 && fvhip_set_rank(h, rank, nranks)) throw std::runtime_error(g_err);
 		if(nranks != h->nparts || rank != h->rank)
 			throw std::invalid_argument("communicator does not match the handle's partition");
@@ -333,6 +344,7 @@ int fvhip_group_create(fvhip_handle* hs, int n, fvhip_group* out)
 		std::unique_ptr<fvhip_group_s> g(new fvhip_group_s());
 		std::vector<int> seen(n, 0);
 		for(int i = 0; i < n; i++) {
+			if(hs[i] && hs[i]->periodic) throw std::invalid_argument("fvhip_group_create: a periodic handle cannot join a group");
 			if(!hs[i] || hs[i]->nparts != n || hs[i]->rank < 0 || hs[i]->rank >= n || seen[hs[i]->rank]++)
 				throw std::invalid_argument("a group needs one handle per rank of one partition");
 			g->hs.push_back(hs[i]);
@@ -367,6 +379,20 @@ int fvhip_trace_exchange_device(fvhip_handle h, const double* d_left, double* d_
 		need(d_left, "left trace"); need(d_right, "right trace");
 		HC(hipSetDevice(h->device));
 		h->trace_exchange_rccl(d_left, d_right, width);
+		HC(hipStreamSynchronize(h->stream));
+	});
+}
+
+int fvhip_ghost_update_device(fvhip_handle h, double* d_arr, int width)
+{
+	return guard([&] {
+		need(h, "handle");
+		need(d_arr, "array");
+		if(width < 1 || width > 8) throw std::invalid_argument("fvhip_ghost_update_device: width must be 1..8");
+		if(!h->halo()) return;
+		if(h->in_group) throw std::runtime_error("handle belongs to a group: use the fvhip_group_* entry point");
+		HC(hipSetDevice(h->device));
+		h->exchange_rccl(d_arr, width);
 		HC(hipStreamSynchronize(h->stream));
 	});
 }
@@ -540,7 +566,7 @@ int fvhip_entropy_error_device(fvhip_handle h, const double* d_u, double* err)
 		HC(hipSetDevice(h->device));
 		double* out = entropySum(h, d_u);
 		if(h->comm) NC(ncclAllReduce(out, out, 1, ncclDouble, ncclSum, h->comm, h->stream));   // mpi_all_reduce :49
-		else if(h->halo()) throw std::runtime_error("partitioned handle: call fvhip_comm_init (or use a group) first");
+		else if(h->needsComm()) throw std::runtime_error("partitioned handle: call fvhip_comm_init (or use a group) first");
 		double s = 0;
 		HC(hipMemcpyAsync(&s, out, sizeof s, hipMemcpyDeviceToHost, h->stream));
 		HC(hipStreamSynchronize(h->stream));
@@ -705,7 +731,7 @@ int fvhip_matfree_apply(fvhip_handle h, const double* x, double* y)
 		if(h->halo()) {
 			// partitioned: the operator over all ranks (global |x|; ghost rows of the perturbed state
 			// are exchanged inside the residual), as fvhip_matfree_apply_device does
-			if(!h->comm) throw std::runtime_error("partitioned handle: call fvhip_comm_init first");
+			if(h->needsComm()) throw std::runtime_error("partitioned handle: call fvhip_comm_init first");
 			sysMatfree({h}, fvhip_ctx::GroupExchange(), {dx}, {dy});
 		} else h->matfree(dx, dy);
 		downloadReference(h, dy, y, 4);
@@ -724,7 +750,7 @@ int fvhip_matfree_apply_device(fvhip_handle h, const double* d_x, double* d_y)
 		need(d_x, "x"); need(d_y, "y");
 		HC(hipSetDevice(h->device));
 		if(!h->halo()) { h->matfree(d_x, d_y); return; }
-		if(!h->comm) throw std::runtime_error("partitioned handle: call fvhip_comm_init (or use a group) first");
+		if(h->needsComm()) throw std::runtime_error("partitioned handle: call fvhip_comm_init (or use a group) first");
 		sysMatfree({h}, fvhip_ctx::GroupExchange(), {d_x}, {d_y});
 	});
 }
@@ -870,7 +896,8 @@ int fvhip_layout_probe(const fvhip_mesh* mesh, const fvhip_flow_config* cfg, lon
 	return guard([&] {
 		if(!mesh || !cfg || !s) throw std::invalid_argument("null argument");
 		checkConfig(cfg);
-		const Layout L = buildLayout(topoFromMesh(*mesh), *cfg, true);
+		// a mesh with connectivity faces (one rank's subdomain, or a periodic mesh) as fvhip_create lays it out
+		const Layout L = buildLayout(mesh->nconnface > 0 ? topoFromRankMesh(*mesh) : topoFromMesh(*mesh), *cfg, true);
 		layoutStats(L, s, 16);
 	});
 }
@@ -954,6 +981,7 @@ int fvmesh_generate(int kind, int a, int b, int c, double x, double y, double z,
 		else if(kind == 1) m->raw = generateCylinderOgrid(a, b, x, y);
 		else if(kind == 2) m->raw = generateFlatPlate(a, b, x, y, z);
 		else if(kind == 3) m->raw = generateNacaCgrid(a, static_cast<int>(z), b, c, x, y);
+		else if(kind == 4) m->raw = generatePeriodicBox(a, b, c, x, y, z);
 		else throw std::invalid_argument("unknown mesh kind");
 		m->mesh = buildMesh(m->raw);
 		*out = m.release();
@@ -1011,6 +1039,26 @@ int fvmesh_restrict(fvmesh_handle g, const int* elemdist, int rank, fvmesh_handl
 		if(!g || !elemdist || !out) throw std::invalid_argument("null argument");
 		std::unique_ptr<fvmesh_s> m(new fvmesh_s());
 		m->mesh = restrictMesh(g->mesh, elemdist, rank);
+		m->raw = m->mesh.md;
+		*out = m.release();
+	});
+}
+
+int fvmesh_periodic_map(fvmesh_handle m, int marker, int axis, int* map)
+{
+	return guard([&] {
+		if(!m || !map) throw std::invalid_argument("null argument");
+		const std::vector<int> pm = periodicMap(m->mesh, marker, axis);
+		std::copy(pm.begin(), pm.end(), map);
+	});
+}
+
+int fvmesh_periodic(fvmesh_handle g, int npairs, const int* markers, const int* axes, fvmesh_handle* out)
+{
+	return guard([&] {
+		if(!g || !markers || !axes || !out) throw std::invalid_argument("null argument");
+		std::unique_ptr<fvmesh_s> m(new fvmesh_s());
+		m->mesh = makePeriodic(g->mesh, npairs, markers, axes);
 		m->raw = m->mesh.md;
 		*out = m.release();
 	});

@@ -80,7 +80,7 @@ struct System
 inline System single(fvhip_ctx* h)
 {
 	if(h->in_group) throw std::runtime_error("handle belongs to a group: use the fvhip_group_* entry point");
-	if(h->halo() && !h->comm) throw std::runtime_error("partitioned handle: call fvhip_comm_init (or use a group) first");
+	if(h->needsComm()) throw std::runtime_error("partitioned handle: call fvhip_comm_init (or use a group) first");
 	return System{{h}, {}};
 }
 

@@ -13,6 +13,7 @@
 #include <stdexcept>
 #include <algorithm>
 #include <numeric>
+#include <random>
 
 namespace fvhip {
 
@@ -546,8 +547,150 @@ Mesh restrictMesh(const Mesh& gm, const int* elemdist, int rank)
 }
 
 // ------------------------------------------------------------------------------------------------
+// Periodic boundaries
+// ------------------------------------------------------------------------------------------------
+
+/// UMesh::compute_periodic_map (mesh.cpp:369-424): the boundary faces of marker `marker` are paired by the
+/// coordinate 1 - axis of their midpoints. A face not yet paired takes the first later face of the marker,
+/// itself not yet paired, whose coordinate lies within 1e-8 (absolute, mesh.cpp:409) of its own.
+std::vector<int> periodicMap(const Mesh& m, int marker, int axis)
+{
+	if(axis != 0 && axis != 1) throw std::invalid_argument("periodic map: axis must be 0 or 1");
+	const int nb = m.md.nbface, ax = 1 - axis;
+	std::vector<int> map(nb, -1);
+	auto mid = [&](int f) {
+		return (m.md.coords[2*static_cast<size_t>(m.intfac[4*static_cast<size_t>(f)+2])+ax] +
+		        m.md.coords[2*static_cast<size_t>(m.intfac[4*static_cast<size_t>(f)+3])+ax])/2.0;
+	};
+	auto tag = [&](int f) { return m.md.nbtag > 0 ? m.btags[static_cast<size_t>(f)*m.md.nbtag] : 0; };
+	for(int i = 0; i < nb; i++) {
+		if(tag(i) != marker || map[i] > -1) continue;
+		const double ci = mid(i);
+		for(int j = i+1; j < nb; j++) {
+			if(tag(j) != marker || map[j] > -1) continue;
+			if(std::fabs(ci - mid(j)) <= 1e-8) { map[i] = j; map[j] = i; break; }
+		}
+	}
+	return map;
+}
+
+Mesh makePeriodic(const Mesh& gm, int npairs, const int* markers, const int* axes)
+{
+	if(gm.nconnface != 0) throw std::runtime_error("periodic: the mesh already has connectivity faces");
+	if(npairs < 1) throw std::invalid_argument("periodic: no (marker, axis) pair given");
+	const MeshData& g = gm.md;
+	const int nb = g.nbface, N = g.nelem, mf = g.maxnfael;
+	std::vector<int> partner(nb, -1);
+	for(int p = 0; p < npairs; p++) {
+		const std::vector<int> map = periodicMap(gm, markers[p], axes[p]);
+		int found = 0;
+		for(int i = 0; i < nb; i++) {
+			if(g.nbtag == 0 || gm.btags[static_cast<size_t>(i)*g.nbtag] != markers[p]) continue;
+			found++;
+			if(map[i] < 0) throw std::runtime_error("periodic: boundary face " + std::to_string(i) + " of marker "
+			                                        + std::to_string(markers[p]) + " has no partner");
+			if(partner[i] >= 0 && partner[i] != map[i])
+				throw std::runtime_error("periodic: marker " + std::to_string(markers[p]) + " is given twice");
+			partner[i] = map[i];
+		}
+		if(!found) throw std::runtime_error("periodic: no boundary face carries marker " + std::to_string(markers[p]));
+	}
+	for(int i = 0; i < nb; i++) {
+		const int j = partner[i];
+		if(j < i) continue;                      // unpaired, or checked from the partner's side
+		const double *mi = &gm.facemetric[3*static_cast<size_t>(i)], *mj = &gm.facemetric[3*static_cast<size_t>(j)];
+		const std::string who = "periodic: boundary faces " + std::to_string(i) + " and " + std::to_string(j);
+		if(std::fabs(mi[2] - mj[2]) > 1e-8*mi[2]) throw std::runtime_error(who + " differ in length");
+		if(std::fabs(mi[0] + mj[0]) > 1e-8 || std::fabs(mi[1] + mj[1]) > 1e-8)
+			throw std::runtime_error(who + " do not have opposite normals");
+		if(gm.intfac[4*static_cast<size_t>(i)] == gm.intfac[4*static_cast<size_t>(j)])
+			throw std::runtime_error(who + " belong to the same cell " + std::to_string(gm.intfac[4*static_cast<size_t>(i)])
+			                         + " (one cell across the period)");
+	}
+	// the remaining physical boundary faces in their old relative order; points and cells as they are
+	MeshData md = g;
+	const int bw = g.nnofa + g.nbtag;
+	md.bface.clear(); md.nbface = 0;
+	std::vector<int> cf;
+	for(int i = 0; i < nb; i++) {
+		if(partner[i] < 0) {
+			md.bface.insert(md.bface.end(), g.bface.begin() + static_cast<size_t>(i)*bw, g.bface.begin() + static_cast<size_t>(i+1)*bw);
+			md.nbface++;
+			continue;
+		}
+		const int cell = gm.intfac[4*static_cast<size_t>(i)];
+		int lf = -1;
+		for(int k = 0; k < g.nfael[cell]; k++) if(gm.elemface[static_cast<size_t>(cell)*mf+k] == i) lf = k;
+		if(lf < 0) throw std::logic_error("periodic: boundary face is not a face of its cell");
+		const int c5[5] = {cell, lf, -1, gm.intfac[4*static_cast<size_t>(partner[i])], std::min(i, partner[i])};
+		cf.insert(cf.end(), c5, c5+5);
+	}
+	Mesh M;
+	buildTopology(std::move(md), M, cf);
+	// ghost rows: the partner cell's centre displaced by the period (this face's midpoint - the partner's)
+	int ic = 0;
+	for(int i = 0; i < nb; i++) {
+		if(partner[i] < 0) continue;
+		const int j = partner[i], pc = gm.intfac[4*static_cast<size_t>(j)];
+		for(int d = 0; d < 2; d++)
+			M.rc[2*(static_cast<size_t>(N)+ic)+d] = gm.rc[2*static_cast<size_t>(pc)+d]
+				+ (gm.gr[2*static_cast<size_t>(i)+d] - gm.gr[2*static_cast<size_t>(j)+d]);
+		ic++;
+	}
+	return M;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Synthetic meshes
 // ------------------------------------------------------------------------------------------------
+
+MeshData generatePeriodicBox(int nx, int ny, int flags, double lx, double ly, double jitter)
+{
+	if(nx < 1 || ny < 1) throw std::invalid_argument("periodic box: needs at least one cell each way");
+	if(!(lx > 0 && ly > 0)) throw std::invalid_argument("periodic box: the extents must be positive");
+	if(!(jitter >= 0 && jitter <= 0.3)) throw std::invalid_argument("periodic box: jitter must lie in [0, 0.3]");
+	const bool tri = (flags & 1) != 0, wrapy = (flags & 2) != 0;
+	MeshData m;
+	m.npoin = (nx+1)*(ny+1);
+	m.coords.resize(static_cast<size_t>(m.npoin)*2);
+	auto P = [&](int i, int j) { return j*(nx+1) + i; };
+	const double hx = lx/nx, hy = ly/ny, amp = jitter*std::min(hx, hy);
+	std::mt19937_64 rng(42);
+	auto draw = [&]() { return static_cast<double>(rng() >> 11)*(2.0/9007199254740992.0) - 1.0; };   // [-1, 1)
+	for(int j = 0; j <= ny; j++)
+		for(int i = 0; i <= nx; i++) {
+			const size_t p = static_cast<size_t>(P(i,j));
+			m.coords[2*p] = i == nx ? lx : i*hx;
+			m.coords[2*p+1] = j == ny ? ly : j*hy;
+			if(amp > 0 && i > 0 && i < nx && j > 0 && j < ny) {
+				const double dx = draw(), dy = draw();
+				m.coords[2*p] += amp*dx; m.coords[2*p+1] += amp*dy;
+			}
+		}
+	for(int j = 0; j < ny; j++)
+		for(int i = 0; i < nx; i++) {
+			const int a = P(i,j), b = P(i+1,j), c = P(i+1,j+1), d = P(i,j+1);
+			if(!tri) {
+				m.inpoel.insert(m.inpoel.end(), {a, b, c, d});
+				m.nnode.push_back(4); m.nfael.push_back(4);
+			} else {
+				if((i + j) % 2 == 0) m.inpoel.insert(m.inpoel.end(), {a, b, c, a, c, d});
+				else m.inpoel.insert(m.inpoel.end(), {a, b, d, b, c, d});
+				m.nnode.push_back(3); m.nfael.push_back(3);
+				m.nnode.push_back(3); m.nfael.push_back(3);
+			}
+		}
+	m.nelem = static_cast<int>(m.nnode.size());
+	m.maxnnode = tri ? 3 : 4; m.maxnfael = m.maxnnode; m.nnofa = 2; m.nbtag = 2; m.ndtag = 2;
+	m.vol_regions.assign(static_cast<size_t>(m.nelem)*2, 1);
+	auto addb = [&](int a, int b, int tag) { m.bface.insert(m.bface.end(), {a, b, tag, 1}); };
+	for(int i = 0; i < nx; i++) addb(P(i,0), P(i+1,0), wrapy ? 5 : 2);         // y = 0
+	for(int j = 0; j < ny; j++) addb(P(nx,j), P(nx,j+1), 4);                   // x = lx
+	for(int i = nx; i > 0; i--) addb(P(i,ny), P(i-1,ny), wrapy ? 5 : 3);       // y = ly
+	for(int j = ny; j > 0; j--) addb(P(0,j), P(0,j-1), 4);                     // x = 0
+	m.nbface = static_cast<int>(m.bface.size()/4);
+	return m;
+}
 
 namespace {
 

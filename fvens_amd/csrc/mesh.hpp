@@ -80,6 +80,29 @@ std::vector<int> partitionTrivial(int nelem, int nranks);
 /// hold the centres of the neighbouring cells (what the Spatial ctor's ghost scatter puts there)
 Mesh restrictMesh(const Mesh& gm, const int* elemdist, int rank);
 
+/// UMesh::compute_periodic_map (mesh.cpp:369-424) restated: pairs the boundary faces of `marker` whose
+/// midpoints agree in the coordinate 1 - axis to 1e-8; map[iface] = the partner's boundary-face index, -1
+/// for an unpaired face and for every face of another marker. (The reference also rewrites the paired
+/// faces' right cells, which no flow code of its reads, abc.hpp:3; here makePeriodic consumes the map.)
+std::vector<int> periodicMap(const Mesh& m, int marker, int axis);
+
+/// The mesh with the faces of `markers` (paired by periodicMap along `axes`) turned into connectivity
+/// faces of the mesh with itself, in the reference's face order (mesh.cpp:659-762): the remaining physical
+/// boundary faces in their old relative order, the interior faces unchanged, then the former periodic
+/// faces in their old boundary-face order with R = nelem + icface. connface[ic] = {cell, local face, -1
+/// ("this rank itself"), the partner's cell, pair id = the smaller old boundary-face index of the two};
+/// rc[nelem + ic] = the partner cell's centre + (this face's midpoint - the partner face's midpoint).
+/// Refuses an unpaired marker face, partners of different length or without opposite normals (1e-8), a
+/// face whose partner belongs to the same cell, and a mesh that already has connectivity faces.
+Mesh makePeriodic(const Mesh& gm, int npairs, const int* markers, const int* axes);
+
+/// Periodic test box on [0,lx] x [0,ly] with nx x ny cells. flags bit 0: every quadrangle split into two
+/// triangles, the diagonal alternating with the parity of i + j; bit 1: y = 0 and y = ly both carry marker 5
+/// (else 2 and 3: the walls of the reference's Couette deck, tests/visc-couette/implicit.ctrl). x = 0 and
+/// x = lx carry marker 4. jitter in [0, 0.3]: interior points are displaced by jitter*min(hx, hy) times a
+/// std::mt19937_64 (seed 42) draw in [-1, 1)^2, row by row; boundary points stay put.
+MeshData generatePeriodicBox(int nx, int ny, int flags, double lx, double ly, double jitter);
+
 /// Synthetic hybrid O-grid around a NACA 0012 aerofoil (chord 1, LE at origin).
 /// ntheta points around the surface, nquad quad layers at the wall, ntri triangle-split layers
 /// outside them, outer circle radius rfar about (0.5,0). Wall marker 2, farfield marker 4.

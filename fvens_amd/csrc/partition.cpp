@@ -383,6 +383,11 @@ MeshTopo topoFromRankMesh(const fvhip_mesh& m)
 	checkLinearCells(m, "per-rank mesh");
 	const int cs = F - nc;                                  // gConnBFaceStart
 	auto C = [&](int ic, int k) { return m.connface[5*static_cast<size_t>(ic)+k]; };
+	// neighbour rank -1 is the mesh itself (a periodic pair, makePeriodic): all faces or none
+	int nself = 0;
+	for(int ic = 0; ic < nc; ic++) if(C(ic,2) == -1) nself++;
+	if(nself != 0 && nself != nc) throw std::invalid_argument("periodic faces on a partitioned mesh are not supported");
+	const bool periodic = nself == nc;
 	std::vector<int> order(nc);
 	std::iota(order.begin(), order.end(), 0);
 	std::sort(order.begin(), order.end(), [&](int a, int b) {
@@ -438,6 +443,24 @@ MeshTopo topoFromRankMesh(const fvhip_mesh& m)
 	// neighbour ranks and the exchange lists
 	T.ghost_start.push_back(0);
 	T.send_start.push_back(0);
+	if(periodic) {
+		// the mesh is its own neighbour: the sort key (rank, pair id, index) put the two sides of a pair next to
+		// each other, and each side's ghost receives the other side's cell
+		if(nc % 2) throw std::invalid_argument("periodic mesh: connectivity faces do not come in pairs");
+		T.nbr_rank.push_back(-1);
+		T.send_cells.resize(nc);
+		for(int i = 0; i < nc; i += 2) {
+			const int a = order[i], b = order[i+1];
+			if(C(a,4) != C(b,4) || C(a,3) != C(b,0) || C(b,3) != C(a,0) || C(a,0) == C(b,0))
+				throw std::invalid_argument("periodic mesh: connectivity faces " + std::to_string(a) + " and "
+				                            + std::to_string(b) + " are not the two sides of one pair");
+			T.send_cells[i] = C(b,0);
+			T.send_cells[i+1] = C(a,0);
+		}
+		T.ghost_start.push_back(nc);
+		T.send_start.push_back(nc);
+		return T;
+	}
 	for(int i = 0; i < nc; i++) {
 		const int q = C(order[i], 2);
 		if(T.nbr_rank.empty() || T.nbr_rank.back() != q) {

@@ -76,6 +76,10 @@ MeshTopo topoFromMesh(const fvhip_mesh& m);
 /// exchange agree without the index handshake of L2TraceVector::update_comm_pattern
 /// (tracevector.cpp:31-184). The result is the reference's per-rank residual: faces, orientation
 /// and accumulation order are the subdomain's own.
+/// A periodic mesh (makePeriodic: every connectivity face names rank -1, the mesh itself) is its own single
+/// neighbour: nbr_rank = {-1}, ghosts ordered by (pair id connface(.,4), icface) so that the two sides of a
+/// pair are adjacent, and send_cells[g] = the cell whose row ghost g receives (the other side's cell). A mesh
+/// mixing rank -1 with real ranks is refused.
 MeshTopo topoFromRankMesh(const fvhip_mesh& m);
 
 /// Rank `rank`'s piece of a single-domain mesh partitioned by `part` (part[cell] in [0,nparts)),

@@ -89,6 +89,11 @@ inline int reconstructionFromName(const std::string& s) {
 }
 
 /// Device-resident FlowFV. u is the ghosted state [nelem+nconnface][4] in the mesh's numbering.
+/// A periodic mesh goes through the same class: fvmesh_periodic(mesh, npairs, markers, axes, &pm) turns the
+/// periodic markers' face pairs into connectivity faces of the mesh with itself (neighbour rank -1),
+/// fvmesh_view(pm, &view) fills the fvhip_mesh passed here, and the boundary conditions list only the markers
+/// that are left. No rank, communicator or group: the library fills the ghost rows itself (ghost_update_device
+/// for the caller's own ghosted device arrays, the reference's VecGhostUpdate).
 class FlowFV_HIP
 {
 public:
@@ -163,6 +168,9 @@ public:
 		return p;
 	}
 	void synchronize() const { check(fvhip_synchronize(h)); }
+	/// VecGhostUpdate (alinalg.cpp:17-29) of a device cell array [nelem+nconnface][width] in internal order,
+	/// width 1..8: a gather on a periodic handle, the RCCL exchange on a rank, nothing without ghost rows
+	void ghost_update_device(double* d_arr, int width) const { check(fvhip_ghost_update_device(h, d_arr, width)); }
 
 private:
 	fvhip_mesh m;

@@ -102,7 +102,8 @@ typedef struct fvhip_mesh {
 	const double* rcbp;       /* [nbface][2] */
 	const double* gr;         /* [naface][2] */
 	const int* connface;      /* [nconnface][5] gconnface (mesh.hpp:60-70): cell, local face, neighbour's
-	                             rank, global neighbour cell, global face; NULL when nconnface == 0 */
+	                             rank, global neighbour cell, global face; NULL when nconnface == 0. A periodic
+	                             mesh (fvmesh_periodic): rank -1, the partner's cell, the pair id */
 } fvhip_mesh;
 
 typedef struct fvhip_ctx* fvhip_handle;
@@ -123,7 +124,14 @@ int fvhip_device_count(void);
  *  of the reference (flow_spatial.cpp:636-816 with its connectivity faces; the face traces and ghost
  *  gradients L2TraceVector / VecGhostUpdate exchange, tracevector.cpp:213-340, alinalg.cpp:17-29, come
  *  from the library's RCCL exchange), once fvhip_comm_init (or fvhip_set_rank + a group) gave the rank.
- *  Ghost rows of u are refreshed by the library's exchange (the rows the caller's VecGhostUpdate holds). */
+ *  Ghost rows of u are refreshed by the library's exchange (the rows the caller's VecGhostUpdate holds).
+ *  A mesh whose connectivity faces all name rank -1 (fvmesh_periodic) gives a periodic handle: rank 0 of 1,
+ *  every exchange a gather on the handle's own device (k_ghost_gather), so no communicator and no group is
+ *  needed and fvhip_set_rank, fvhip_comm_init and fvhip_group_create refuse it. Device arrays with ghost rows
+ *  hold them after the owned rows in the order of (pair id connface(.,4), connectivity-face index): the two
+ *  sides of a pair are adjacent. Preconditioners drop the couplings to ghost cells, as they do across ranks:
+ *  lines, ILU and Gauss-Seidel stop at the periodic seam, the operator does not. A mesh mixing rank -1 with
+ *  real ranks is refused ("periodic faces on a partitioned mesh are not supported"). */
 int fvhip_create(const fvhip_mesh* mesh, const fvhip_flow_config* cfg, int device, fvhip_handle* out);
 /** Rank of a per-rank-mesh handle within nranks (PETSC_COMM_WORLD's rank in the reference); needed
  *  before fvhip_group_create, implied by fvhip_comm_init */
@@ -185,8 +193,14 @@ int fvhip_group_create(fvhip_handle* handles, int n, fvhip_group* out);
 /** L2TraceVector::updateSharedFacesBegin + End (linalg/tracevector.cpp:213-340) on a per-rank mesh
  *  (nconnface > 0): d_left [nconnface][width] (device, the mesh's connectivity-face order) holds this
  *  rank's face values; on return d_right[icface] holds the neighbour rank's value of the same face
- *  (its left). width 1..4. RCCL ranks (fvhip_comm_init) / all ranks of a group in one process. */
+ *  (its left). width 1..4. RCCL ranks (fvhip_comm_init) / all ranks of a group in one process.
+ *  A periodic handle needs neither: d_right[icface] = d_left[the partner's icface] by one gather. */
 int fvhip_trace_exchange_device(fvhip_handle h, const double* d_left, double* d_right, int width);
+/** VecGhostUpdate (linalg/alinalg.cpp:17-29) of a device cell array d_arr [ncell + nghost][width] in internal
+ *  order, width 1..8: the ghost rows receive the rows of the cells they stand for. A periodic handle runs one
+ *  gather on the device, an RCCL rank (fvhip_comm_init) the exchange with its neighbours; on a handle without
+ *  ghost rows nothing happens. fvhip_block_apply_device reads the ghost rows of x, so its caller runs this first. */
+int fvhip_ghost_update_device(fvhip_handle h, double* d_arr, int width);
 int fvhip_group_trace_exchange_device(fvhip_group g, const double* const* d_left, double* const* d_right, int width);
 int fvhip_group_destroy(fvhip_group g);
 int fvhip_group_compute_residual_device(fvhip_group g, const double* const* d_u, double* const* d_r,
@@ -512,7 +526,13 @@ int fvmesh_read_gmsh(const char* path, fvmesh_handle* out);
  *        1 = cylinder triangle O-grid (a=ntheta, b=nr, x=r0, y=r1)
  *        2 = flat plate quads (a=nx, b=ny, x=lead length, y=height, z=wall spacing)
  *        3 = NACA 0012 C-grid (a=nsurf, b=nquad, c=ntri, x=rfar, y=wall spacing, z=nwake: columns along
- *            each wake; 2 nwake + nsurf columns of cells) */
+ *            each wake; 2 nwake + nsurf columns of cells)
+ *        4 = periodic test box on [0,x] x [0,y] with a x b cells. c bit 0: every quadrangle split into two
+ *            triangles, the diagonal alternating with the parity of i + j; c bit 1: y = 0 and y = y-extent both
+ *            carry marker 5, otherwise markers 2 and 3 (the walls of tests/visc-couette/implicit.ctrl); x = 0
+ *            and x = x-extent carry marker 4. z in [0, 0.3] displaces interior points by z min(hx, hy) times a
+ *            std::mt19937_64 (seed 42) draw in [-1, 1)^2; boundary points stay put. The box is an ordinary
+ *            mesh: fvmesh_periodic turns markers 4 (axis 0) and 5 (axis 1) into periodic pairs */
 int fvmesh_generate(int kind, int a, int b, int c, double x, double y, double z, fvmesh_handle* out);
 /** NACA 0012 hybrid mesh of the visc-naca0012 grids' topology (testcases/visc-naca0012/grids/
  *  naca0012nasa-blcirc.geo, NACA0012_lam_hybrid_1.msh: a quadrangle block round the body, triangles
@@ -536,6 +556,27 @@ int fvmesh_partition_trivial(int nelem, int nranks, int* elemdist);
  *  distribution elemdist [nelem of g], with its connectivity faces; rc has nelem+nconnface rows, the
  *  ghost rows holding the neighbouring cells' centres (the Spatial ctor's ghost scatter, aspatial.cpp:41-66) */
 int fvmesh_restrict(fvmesh_handle g, const int* elemdist, int rank, fvmesh_handle* out);
+/** UMesh::compute_periodic_map (mesh/mesh.cpp:369-424) restated: of the boundary faces of `marker`, a face not
+ *  yet paired takes the first later unpaired face whose midpoint agrees with its own in the coordinate
+ *  1 - axis to 1e-8 (:384, :398-409). map [nbface]: the partner's boundary-face index, -1 for an unpaired
+ *  face or a face of another marker (the reference's periodicmap, :381, :411-412; its test tests/mesh/
+ *  mesh.cpp:68-85). The reference also overwrites the paired faces' right cells (:416-417), which none of
+ *  its flow code reads (spatial/abc.hpp:3); here fvmesh_periodic consumes the map instead. */
+int fvmesh_periodic_map(fvmesh_handle m, int marker, int axis, int* map);
+/** The mesh with periodic boundaries: the faces of markers[p], paired by fvmesh_periodic_map along axes[p]
+ *  (p < npairs), become connectivity faces of the mesh with itself. Face order as the reference's
+ *  compute_faceConnectivity (mesh/mesh.cpp:659-762, as fvmesh_restrict): the remaining physical boundary faces
+ *  first in their old relative order, the interior faces unchanged, then the former periodic faces in their old
+ *  boundary-face order with intfac(f,1) = nelem + icface; esuel and elemface renumbered to match (physical
+ *  boundary neighbours nelem + nconnface + iface). rc has nelem + nconnface rows: row nelem + ic is the partner
+ *  cell's centre plus (this face's midpoint - the partner face's midpoint), the period vector.
+ *  connface[ic] = {cell, local face, -1, the partner's cell, pair id}: neighbour rank -1 means "this rank
+ *  itself", the pair id is the smaller old boundary-face index of the two sides. Refused, naming the face: a
+ *  marker face left unpaired; partners whose lengths differ by more than 1e-8 of the length or whose normals are
+ *  not opposite to 1e-8; a face whose partner belongs to the same cell (one cell across the period); a mesh
+ *  that already has connectivity faces. fvmesh_restrict, fvhip_partition_* and fvhip_create_partitioned
+ *  refuse the result: periodic faces on several ranks are not supported. */
+int fvmesh_periodic(fvmesh_handle m, int npairs, const int* markers, const int* axes, fvmesh_handle* out);
 /** UMesh::gglobalElemIndex of a subdomain from fvmesh_restrict: gidx [nelem] */
 int fvmesh_global_elem_index(fvmesh_handle m, int* gidx);
 /** Fills a fvhip_mesh view whose pointers stay valid until fvmesh_destroy */
