@@ -3,43 +3,29 @@
  *   host<->device plumbing with the reference's cell numbering, kernel timing, mesh builder.
  * No exception crosses the ABI; errors become a nonzero return and fvhip_last_error().
  */
-#include "ctx.hpp"
+#include "system.hpp"
 
 #include <cmath>
 
-namespace fvhip_detail {
-
-fvhip_ctx::GroupExchange groupExchange(const fvhip_group_s* g)
+/// getGradients (flow_spatial.cpp:95-112) into d_grad: ghost rows of u for the border cells (partitioned handles),
+/// ghost states from cell values, then the gradient scheme on CONSERVED variables
+static void conservedGradients(fvhip_ctx* h, double* u)
 {
-	// in-process exchange: pack everywhere, then copy each neighbour's packed rows into the ghost block
-	return [g](const fvhip_ctx::ArrayOf& arr_of, int width, int layers) {
-		const std::vector<fvhip_ctx*>& hs = g->hs;
-		const size_t n = hs.size();
-		std::vector<fvhip_ctx*> byrank(n);
-		for(fvhip_ctx* h : hs) byrank[h->rank] = h;
-		for(size_t i = 0; i < n; i++) if(hs[i]->halo()) { HC(hipSetDevice(hs[i]->device)); hs[i]->pack(arr_of(i), width); }
-		for(size_t i = 0; i < n; i++) HC(hipStreamSynchronize(hs[i]->stream));
-		for(size_t i = 0; i < n; i++) {
-			fvhip_ctx* h = hs[i];
-			const Layout& L = h->L;
-			for(size_t k = 0; k < L.nbr_rank.size(); k++) {
-				fvhip_ctx* q = byrank[L.nbr_rank[k]];
-				const Layout& Q = q->L;
-				size_t kk = 0;
-				while(kk < Q.nbr_rank.size() && Q.nbr_rank[kk] != h->rank) kk++;
-				if(kk == Q.nbr_rank.size()) throw std::logic_error("halo lists are not symmetric");
-				const int cnt = h->ghostCount(k, layers);
-				if(cnt != q->sendCount(kk, layers)) throw std::logic_error("halo sizes differ");
-				if(cnt == 0) continue;
-				HC(hipMemcpyAsync(arr_of(i) + static_cast<size_t>(width)*(L.ncell + L.ghost_start[k]),
-				                  q->d_sendbuf + static_cast<size_t>(width)*Q.send_start[kk],
-				                  sizeof(double)*width*static_cast<size_t>(cnt), hipMemcpyDeviceToDevice, h->stream));
-			}
-		}
-		for(size_t i = 0; i < n; i++) HC(hipStreamSynchronize(hs[i]->stream));
-	};
+	h->exchange_rccl(u, 4);
+	exact::launch_prep(h->M, h->P, u, h->d_up, h->d_ubc, h->d_ug, false, h->stream);
+	switch(h->cfg.gradientscheme) {
+		case FVHIP_GRAD_LEASTSQUARES: exact::launch_grad_wls(h->M, u, h->d_ubc, h->d_grad, h->stream); break;
+		case FVHIP_GRAD_GREENGAUSS: exact::launch_grad_gg(h->M, u, h->d_ubc, h->d_grad, h->stream); break;
+		default: exact::launch_fill(h->d_grad, 0.0, 8LL*h->L.ncell, h->stream);
+	}
 }
 
+/// MatrixFreeSpatialJacobian::apply over all ranks of a system (global |x|; the ghost rows of the perturbed state
+/// are exchanged inside the residual)
+static void matfreeOn(System S, const double* const* x, double* const* y)
+{
+	S.each([&](size_t, fvhip_ctx* h) { h->ensureVectors(); });
+	matfreeApply(S, [&](size_t i) { return const_cast<double*>(x[i]); }, [&](size_t i) { return y[i]; });
 }
 
 extern "C" {
@@ -349,6 +335,10 @@ int fvhip_group_create(fvhip_handle* hs, int n, fvhip_group* out)
 				throw std::invalid_argument("a group needs one handle per rank of one partition");
 			g->hs.push_back(hs[i]);
 		}
+		std::vector<const Layout*> Ls;
+		std::vector<int> ranks;
+		for(fvhip_ctx* h : g->hs) { Ls.push_back(&h->L); ranks.push_back(h->rank); }
+		g->legs = haloLegs(Ls, ranks);
 		for(fvhip_ctx* h : g->hs) h->in_group = true;
 		*out = g.release();
 	});
@@ -362,13 +352,10 @@ int fvhip_group_compute_residual_device(fvhip_group g, const double* const* d_u,
 	return guard([&] {
 		need(g, "group");
 		needEach(d_u, g->hs.size(), "u"); needEach(d_r, g->hs.size(), "residual"); if(gettimesteps) needEach(d_dtm, g->hs.size(), "dtm");
-		const size_t n = g->hs.size();
-		std::vector<const double*> us(d_u, d_u + n);
-		std::vector<double*> rs(d_r, d_r + n), dts(n, nullptr);
-		if(gettimesteps) dts.assign(d_dtm, d_dtm + n);
-		fvhip_ctx::residual_seq(g->hs, us, rs, gettimesteps != 0, dts, (flags & FVHIP_RES_OVERWRITE) != 0,
-		                        groupExchange(g));
-		for(size_t i = 0; i < n; i++) HC(hipStreamSynchronize(g->hs[i]->stream));
+		System S = ofGroup(g);
+		const std::vector<double*> none(S.size(), nullptr);
+		residual(S, d_u, d_r, gettimesteps != 0, gettimesteps ? d_dtm : none.data(), (flags & FVHIP_RES_OVERWRITE) != 0);
+		for(fvhip_ctx* h : S.hs) HC(hipStreamSynchronize(h->stream));
 	});
 }
 
@@ -402,32 +389,7 @@ int fvhip_group_trace_exchange_device(fvhip_group g, const double* const* d_left
 	return guard([&] {
 		need(g, "group");
 		needEach(d_left, g->hs.size(), "left trace"); needEach(d_right, g->hs.size(), "right trace");
-		const std::vector<fvhip_ctx*>& hs = g->hs;
-		const size_t n = hs.size();
-		std::vector<fvhip_ctx*> byrank(n);
-		for(fvhip_ctx* h : hs) byrank[h->rank] = h;
-		for(size_t i = 0; i < n; i++) { HC(hipSetDevice(hs[i]->device)); hs[i]->trace_pack(d_left[i], width, hs[i]->stream); }
-		for(size_t i = 0; i < n; i++) HC(hipStreamSynchronize(hs[i]->stream));
-		for(size_t i = 0; i < n; i++) {
-			fvhip_ctx* h = hs[i];
-			const Layout& L = h->L;
-			HC(hipSetDevice(h->device));
-			for(size_t k = 0; k < L.nbr_rank.size(); k++) {
-				fvhip_ctx* q = byrank[L.nbr_rank[k]];
-				const Layout& Q = q->L;
-				size_t kk = 0;
-				while(kk < Q.nbr_rank.size() && Q.nbr_rank[kk] != h->rank) kk++;
-				if(kk == Q.nbr_rank.size()) throw std::logic_error("halo lists are not symmetric");
-				const int cnt = L.ghost_start[k+1] - L.ghost_start[k];
-				if(cnt != Q.send_start[kk+1] - Q.send_start[kk]) throw std::logic_error("halo sizes differ");
-				if(cnt == 0) continue;
-				HC(hipMemcpyAsync(h->d_tracebuf + static_cast<size_t>(width)*L.ghost_start[k],
-				                  q->d_sendbuf + static_cast<size_t>(width)*Q.send_start[kk],
-				                  sizeof(double)*width*static_cast<size_t>(cnt), hipMemcpyDeviceToDevice, h->stream));
-			}
-			h->trace_unpack(d_right[i], width, h->stream);
-		}
-		for(size_t i = 0; i < n; i++) HC(hipStreamSynchronize(hs[i]->stream));
+		ofGroup(g).traceExchange(d_left, d_right, width);
 	});
 }
 
@@ -440,11 +402,7 @@ int fvhip_compute_residual_device(fvhip_handle h, const double* d_u, double* d_r
 		need(h, "handle");
 		need(d_u, "u"); need(d_r, "residual"); if(gettimesteps) need(d_dtm, "dtm");
 		HC(hipSetDevice(h->device));
-		h->use_staged = (flags & FVHIP_RES_STAGED) != 0;
-		h->use_pipe = (flags & FVHIP_RES_PIPELINED) != 0;
-		if(flags & FVHIP_RES_HALO_READY) h->residual_halo_ready(d_u, d_r, gettimesteps != 0, d_dtm, (flags & FVHIP_RES_OVERWRITE) != 0);
-		else h->residual(d_u, d_r, gettimesteps != 0, d_dtm, (flags & FVHIP_RES_OVERWRITE) != 0);
-		h->use_staged = h->use_pipe = false;
+		h->residual(d_u, d_r, gettimesteps != 0, d_dtm, (flags & FVHIP_RES_OVERWRITE) != 0, h->residualPath(flags));
 	});
 }
 
@@ -497,14 +455,7 @@ int fvhip_get_gradients(fvhip_handle h, const double* u, double* grads)
 		need(u, "u"); need(grads, "grads");
 		HC(hipSetDevice(h->device));
 		uploadInternal(h, u, h->d_u, 4);
-		h->exchange_rccl(h->d_u, 4);   // ghost rows for the border cells (partitioned handles)
-		// ghost states from cell values, then the gradient scheme on CONSERVED variables
-		exact::launch_prep(h->M, h->P, h->d_u, h->d_up, h->d_ubc, h->d_ug, false, h->stream);
-		switch(h->cfg.gradientscheme) {
-			case FVHIP_GRAD_LEASTSQUARES: exact::launch_grad_wls(h->M, h->d_u, h->d_ubc, h->d_grad, h->stream); break;
-			case FVHIP_GRAD_GREENGAUSS: exact::launch_grad_gg(h->M, h->d_u, h->d_ubc, h->d_grad, h->stream); break;
-			default: exact::launch_fill(h->d_grad, 0.0, 8LL*h->L.ncell, h->stream);
-		}
+		conservedGradients(h, h->d_u);
 		HC(hipGetLastError());
 		downloadReference(h, h->d_grad, grads, 8);
 	});
@@ -516,18 +467,10 @@ int fvhip_surface_data_device(fvhip_handle h, const double* d_u, int marker, dou
 	return guard([&] {
 		need(h, "handle");
 		need(d_u, "u"); need(funcs, "funcs");
-		if(!funcs) throw std::invalid_argument("funcs must not be NULL");
 		HC(hipSetDevice(h->device));
 		fvhip_ctx::SurfCache& c = h->surfaceFaces(marker);
 		double* u = const_cast<double*>(d_u);
-		h->exchange_rccl(u, 4);   // ghost rows for the border cells' gradients (partitioned handles)
-		// getGradients (flow_spatial.cpp:95-112): ghost states, then the scheme on conserved variables
-		exact::launch_prep(h->M, h->P, u, h->d_up, h->d_ubc, h->d_ug, false, h->stream);
-		switch(h->cfg.gradientscheme) {
-			case FVHIP_GRAD_LEASTSQUARES: exact::launch_grad_wls(h->M, u, h->d_ubc, h->d_grad, h->stream); break;
-			case FVHIP_GRAD_GREENGAUSS: exact::launch_grad_gg(h->M, u, h->d_ubc, h->d_grad, h->stream); break;
-			default: exact::launch_fill(h->d_grad, 0.0, 8LL*h->L.ncell, h->stream);
-		}
+		conservedGradients(h, u);
 		// flowDirectionVector(aoa) with zero side-slip and getFreestreamPressure, on the host as there
 		const double aoa = h->cfg.aoa;
 		const double wx = std::cos(aoa)*std::cos(0.0), wy = std::sin(aoa)*std::cos(0.0);      // mathutils.hpp:67-75
@@ -597,7 +540,7 @@ int fvhip_assemble_jacobian(fvhip_handle h, const double* u, double* diag, doubl
 {
 	return guard([&] {
 		need(h, "handle");
-		need(u, "u"); need(diag, "diag"); if(h->L.ninface > 0) { need(lower, "lower"); need(upper, "upper"); }
+		need(u, "u"); needBlocks(h->L.ninface, diag, lower, upper);
 		HC(hipSetDevice(h->device));
 		const size_t N = static_cast<size_t>(h->L.ncell), Fi = static_cast<size_t>(h->L.ninface);
 		uploadInternal(h, u, h->d_u, 4);
@@ -661,7 +604,7 @@ int fvhip_jacobian_pattern(fvhip_handle h, int* rowptr, int* colind)
 	return guard([&] {
 		need(h, "handle");
 		need(rowptr, "rowptr"); need(colind, "colind");
-		const int N = h->L.ncell, nb = h->L.nbface, Fi = h->L.ninface;
+		const int N = h->L.ncell, Fi = h->L.ninface;
 		// reference cell numbering: diagonal plus one block per interior face on each side
 		std::vector<int> cnt(N, 1);
 		for(int fi = 0; fi < Fi; fi++) { cnt[h->L.perm[h->L.if_L[fi]]]++; cnt[h->L.perm[h->L.if_R[fi]]]++; }
@@ -674,7 +617,6 @@ int fvhip_jacobian_pattern(fvhip_handle h, int* rowptr, int* colind)
 			colind[pos[l]++] = r; colind[pos[r]++] = l;
 		}
 		for(int c = 0; c < N; c++) std::sort(colind + rowptr[c], colind + rowptr[c+1]);
-		(void)nb;
 	});
 }
 
@@ -732,7 +674,7 @@ int fvhip_matfree_apply(fvhip_handle h, const double* x, double* y)
 			// partitioned: the operator over all ranks (global |x|; ghost rows of the perturbed state
 			// are exchanged inside the residual), as fvhip_matfree_apply_device does
 			if(h->needsComm()) throw std::runtime_error("partitioned handle: call fvhip_comm_init first");
-			sysMatfree({h}, fvhip_ctx::GroupExchange(), {dx}, {dy});
+			matfreeOn(System{{h}}, &dx, &dy);
 		} else h->matfree(dx, dy);
 		downloadReference(h, dy, y, 4);
 	});
@@ -751,7 +693,7 @@ int fvhip_matfree_apply_device(fvhip_handle h, const double* d_x, double* d_y)
 		HC(hipSetDevice(h->device));
 		if(!h->halo()) { h->matfree(d_x, d_y); return; }
 		if(h->needsComm()) throw std::runtime_error("partitioned handle: call fvhip_comm_init (or use a group) first");
-		sysMatfree({h}, fvhip_ctx::GroupExchange(), {d_x}, {d_y});
+		matfreeOn(System{{h}}, &d_x, &d_y);
 	});
 }
 
@@ -770,8 +712,7 @@ int fvhip_group_matfree_apply_device(fvhip_group g, const double* const* d_x, do
 	return guard([&] {
 		need(g, "group");
 		needEach(d_x, g->hs.size(), "x"); needEach(d_y, g->hs.size(), "y");
-		const size_t n = g->hs.size();
-		sysMatfree(g->hs, groupExchange(g), std::vector<const double*>(d_x, d_x + n), std::vector<double*>(d_y, d_y + n));
+		matfreeOn(ofGroup(g), d_x, d_y);
 	});
 }
 

@@ -1,7 +1,7 @@
 /** \file implicit.cpp
  * \brief Device-resident pseudo-time solvers over one global system:
  *   SteadyForwardEulerSolver::solve (aodesolver.cpp:135-282) and SteadyBackwardEulerSolver::solve
- *   (aodesolver.cpp:363-638), plus the partitioned matrix-free operator.
+ *   (aodesolver.cpp:363-638), plus the matrix-free operator over a system.
  *
  * The reference hands each linear system to PETSc (KSPSolve, aodesolver.cpp:483; GMRES with a
  * block-Jacobi/ILU or SOR preconditioner from the .solverc files). Here it is solved on the device
@@ -15,7 +15,7 @@
  * uses the assembled blocks as preconditioner, as the reference's KSPSetOperators(A_mf, M) does
  * (casesolvers.cpp:170).
  *
- * A system (linop.hpp) is either one handle (one GPU, or one rank of a partition with its RCCL communicator:
+ * A system (system.hpp) is either one handle (one GPU, or one rank of a partition with its RCCL communicator:
  * partial sums combined by ncclAllReduce) or all ranks of a partition driven from one process (a
  * group: halo rows by device copies, partial sums added on the host in handle order).
  */
@@ -26,7 +26,7 @@
 
 namespace fvhip_detail {
 
-/// |x| is the global norm, the perturbed state gets its ghost rows from the residual's own exchange
+/// the perturbed state gets its ghost rows from the residual's own exchange
 void matfreeApply(System& S, const ArrayOf& x, const ArrayOf& y, bool have_norm)
 {
 	S.each([&](size_t i, fvhip_ctx* h) {
@@ -34,23 +34,21 @@ void matfreeApply(System& S, const ArrayOf& x, const ArrayOf& y, bool have_norm)
 		if(!have_norm) launch_mdot(4LL*h->L.ncell, 0, nullptr, 0, x(i), true, h->iw.part, h->iw.red, h->stream);
 	});
 	if(!have_norm) S.allsumDevice(1);          // |x|^2 stays on the device (launch_pertmag reads it there)
-	if(S.size() == 1 && !S.exg && S.hs[0]->matfreeFusable() && S.hs[0]->matfreeNoAlias(S.hs[0]->mf_u, x(0), y(0))) {
+	if(S.size() == 1 && !S.legs && S.hs[0]->matfreeFusable() && S.hs[0]->matfreeNoAlias(S.hs[0]->mf_u, x(0), y(0))) {
 		// one launch: the perturbed state and the combination inside the residual kernel (bitwise the same)
 		fvhip_ctx* h = S.hs[0];
 		launch_pertmag(h->iw.red, h->mf_eps, h->iw.pm, h->stream);
-		h->matfree_fused(h->mf_u, x(0), h->iw.pm, h->mf_r, h->mf_mdt, y(0));
-		HC(hipGetLastError());
+		h->stage_fused(h->mf_u, y(0), false, nullptr, true, nullptr, 0, nullptr, MfFuse{x(0), h->iw.pm, h->mf_r, h->mf_mdt});
 		return;
 	}
-	std::vector<const double*> aux;
-	std::vector<double*> yg, none(S.size(), nullptr);
+	std::vector<double*> aux, yg, none(S.size(), nullptr);
 	S.each([&](size_t i, fvhip_ctx* h) {
 		launch_pertmag(h->iw.red, h->mf_eps, h->iw.pm, h->stream);
 		launch_mf_perturb(4LL*h->L.ncell, h->mf_u, x(i), h->iw.pm, h->iw.aux, h->stream);
 		aux.push_back(h->iw.aux);
 		yg.push_back(h->iw.yg);
 	});
-	fvhip_ctx::residual_seq(S.hs, aux, yg, false, none, true, S.exg);
+	residual(S, aux.data(), yg.data(), false, none.data(), true);
 	S.each([&](size_t i, fvhip_ctx* h) {
 		launch_mf_combine(h->L.ncell, h->mf_mdt, x(i), h->iw.yg, h->mf_r, h->iw.pm, y(i), h->stream);
 		HC(hipGetLastError());
@@ -357,16 +355,6 @@ static void tvdrk(System& S, const std::vector<double*>& us, int order, double c
 	}
 	if(steps) *steps = step;
 	if(time_out) *time_out = time;
-}
-
-void sysMatfree(const std::vector<fvhip_ctx*>& hs, const fvhip_ctx::GroupExchange& exg,
-                const std::vector<const double*>& x, const std::vector<double*>& y)
-{
-	System S{hs, exg};
-	S.each([&](size_t, fvhip_ctx* h) { h->ensureVectors(); });
-	const ArrayOf xo = [&](size_t i) { return const_cast<double*>(x[i]); };
-	const ArrayOf yo = [&](size_t i) { return y[i]; };
-	matfreeApply(S, xo, yo);
 }
 
 typedef std::vector<double*> States;

@@ -1,96 +1,16 @@
 /** \file linop.hpp
- * \brief One global system (a handle, or all ranks of a partition driven from one process) and the linear
- *   operator and preconditioner of an implicit step on it: the operator and GMRES are in implicit.cpp, the
- *   preconditioner in precond.cpp.
+ * \brief The linear operator and preconditioner of an implicit step on one global system (system.hpp): the
+ *   operator and GMRES are in implicit.cpp, the preconditioner in precond.cpp.
  */
 #ifndef FVHIP_LINOP_HPP
 #define FVHIP_LINOP_HPP
 
-#include "ctx.hpp"
+#include "system.hpp"
 #include "precond_options.hpp"
 
 #include <vector>
 
 namespace fvhip_detail {
-
-struct System
-{
-	std::vector<fvhip_ctx*> hs;
-	fvhip_ctx::GroupExchange exg;        ///< in-process halo transport of a group, else empty
-
-	size_t size() const { return hs.size(); }
-	bool halo() const { return hs[0]->halo(); }
-	template <typename F> void each(F&& f) {
-		for(size_t i = 0; i < hs.size(); i++) { HC(hipSetDevice(hs[i]->device)); f(i, hs[i]); }
-	}
-	void exchange(const fvhip_ctx::ArrayOf& arr, int width) {
-		if(!halo()) return;
-		if(exg) { exg(arr, width, 1); return; }
-		each([&](size_t i, fvhip_ctx* h) { h->exchange_rccl(arr(i), width); });
-	}
-	/// the steppers' residual: every handle's d_r = 0 + (-r(us)) with its local time steps in d_dtm; fills the
-	/// ghost rows of us
-	void residual(const std::vector<double*>& us) {
-		std::vector<const double*> cu(us.begin(), us.end());
-		std::vector<double*> rs, dts;
-		for(fvhip_ctx* h : hs) { rs.push_back(h->d_r); dts.push_back(h->d_dtm); }
-		fvhip_ctx::residual_seq(hs, cu, rs, true, dts, true, exg);
-	}
-	/// global sums of k values every handle left in its iw.red, needed on the device only: one handle
-	/// reduces over its ranks in place (ncclAllReduce, or nothing on one GPU) without a host round trip;
-	/// a group sums on the host (allsum)
-	void allsumDevice(int k) {
-		if(hs.size() == 1) {
-			fvhip_ctx* h = hs[0];
-			if(h->comm) { HC(hipSetDevice(h->device)); NC(ncclAllReduce(h->iw.red, h->iw.red, k, ncclDouble, ncclSum, h->comm, h->stream)); }
-			return;
-		}
-		allsum(k, true);
-	}
-	/// global sums of the k values every handle left in its iw.red: returned on the host and, if
-	/// to_device, present in every handle's iw.red afterwards
-	std::vector<double> allsum(int k, bool to_device) {
-		each([&](size_t, fvhip_ctx* h) {
-			if(h->comm) NC(ncclAllReduce(h->iw.red, h->iw.red, k, ncclDouble, ncclSum, h->comm, h->stream));
-			HC(hipMemcpyAsync(h->iw.h_red, h->iw.red, k*sizeof(double), hipMemcpyDeviceToHost, h->stream));
-		});
-		std::vector<double> tot(k, 0.0);
-		each([&](size_t, fvhip_ctx* h) {
-			HC(hipStreamSynchronize(h->stream));
-			for(int j = 0; j < k; j++) tot[j] += h->iw.h_red[j];
-		});
-		if(hs.size() > 1 && to_device)
-			each([&](size_t, fvhip_ctx* h) {
-				std::copy(tot.begin(), tot.end(), h->iw.h_red);
-				HC(hipMemcpyAsync(h->iw.red, h->iw.h_red, k*sizeof(double), hipMemcpyHostToDevice, h->stream));
-			});
-		return tot;
-	}
-	void sync() { each([&](size_t, fvhip_ctx* h) { HC(hipStreamSynchronize(h->stream)); }); }
-	/// one handle: the global sums of the k values in iw.red, copied to iw.h_red2 behind the reduction
-	/// without waiting (read them after a later wait on the stream)
-	void allsumQueue(int k) {
-		fvhip_ctx* h = hs[0];
-		HC(hipSetDevice(h->device));
-		if(h->comm) NC(ncclAllReduce(h->iw.red, h->iw.red, k, ncclDouble, ncclSum, h->comm, h->stream));
-		HC(hipMemcpyAsync(h->iw.h_red2, h->iw.red, k*sizeof(double), hipMemcpyDeviceToHost, h->stream));
-	}
-};
-
-inline System single(fvhip_ctx* h)
-{
-	if(h->in_group) throw std::runtime_error("handle belongs to a group: use the fvhip_group_* entry point");
-	if(h->needsComm()) throw std::runtime_error("partitioned handle: call fvhip_comm_init (or use a group) first");
-	return System{{h}, {}};
-}
-
-inline System ofGroup(fvhip_group_s* g) { return System{g->hs, groupExchange(g)}; }
-
-typedef fvhip_ctx::ArrayOf ArrayOf;
-
-/// MatrixFreeSpatialJacobian::apply (alinalg.cpp:142-233) over a system (implicit.cpp)
-/// have_norm: |x|^2 is already in iw.red (the line solve that produced x summed it, LinOp::precondition)
-void matfreeApply(System& S, const ArrayOf& x, const ArrayOf& y, bool have_norm = false);
 
 /// `sweeps` smoothing sweeps on level C's A_C x = b from the iterate in x (taken as 0 if `zero`). direction: 0
 /// forward, 1 backward, 2 alternating from forward. smoother 0: colour Gauss-Seidel over the whole level; 1: inside

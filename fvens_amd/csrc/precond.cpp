@@ -291,7 +291,7 @@ void LinOp::iluSweeps(const ArrayOf& v, const ArrayOf& z) {
 /// corrections z += M^-1 (v - A z) (A with the ghost coupling: block-Jacobi across ranks)
 void LinOp::lineSweeps(const ArrayOf& v, const ArrayOf& z, bool want_norm) {
 	// one sweep on one domain for the matrix-free operator: the line solve also returns |z|^2
-	const bool norm = want_norm && o.matfree && o.sweeps == 1 && S.size() == 1 && !S.exg && !S.halo();
+	const bool norm = want_norm && o.matfree && o.sweeps == 1 && S.size() == 1 && !S.legs && !S.halo();
 	S.each([&](size_t i, fvhip_ctx* h) {
 		h->timed("k_line_solve", [&]{ launch_line_solve(h->lines, v(i), z(i), h->stream, norm ? h->iw.red : nullptr); });
 	});

@@ -328,3 +328,57 @@ def test_pipelined_equals_staged_bitwise(meshkey, kind, flux, rec):
     np.testing.assert_array_equal(out[0][1], out[1][1])
     assert np.all(np.isfinite(out[1][0]))
     dev.close()
+
+
+# ------------------------------------------------------------------------------------------------
+# the residual path is an argument of one call: a refused call leaves nothing behind on the handle
+# ------------------------------------------------------------------------------------------------
+def test_refused_call_does_not_change_later_paths():
+    """FVHIP_RES_STAGED | FVHIP_RES_HALO_READY on a partitioned handle is refused after the path is chosen
+    (halo-ready exists for the fused path only). The path used to be handle state that the throwing call left
+    set: fvhip_compute_residual_device itself set it afresh on its next call, every other entry that runs the
+    residual on the handle (the host-pointer entry, the steppers, the matrix-free operator, a group's residual)
+    silently took the staged path from then on. Here the refused call is made on rank 0 of a 3-rank group of the
+    1,792-cell O-grid (WLS + MUSCL, so that the default path is the fused one), and the group's residual after it
+    must still be k_pack + k_grad_ghost + k_residual_wls on every rank, no k_sweep, and the bits it gave before."""
+    import torch
+    m = fa.UMesh.naca_ogrid(64, 12, 8, 20.0, 1e-4)
+    assert m.nelem == 1792
+    p = cases.physics("naca")
+    n = cases.numerics("ROE", "LEASTSQUARES", "VANALBADA")
+    u = cases.state(m, p, 5)
+    part = fa.partition_graph(m, 3)
+    sps = [fa.FlowFV(m, p, n, partition=part, rank=k) for k in range(3)]
+    dus, drs, dts = [], [], []
+    for k, sp in enumerate(sps):
+        g = np.nonzero(part == k)[0][sp.permutation()]
+        x = torch.full((sp.nown + sp.nghost, 4), float("nan"), dtype=torch.float64, device="cuda")
+        x[:sp.nown] = torch.tensor(u[g], device="cuda")
+        dus.append(x)
+        drs.append(torch.zeros((sp.nown, 4), dtype=torch.float64, device="cuda"))
+        dts.append(torch.zeros(sp.nown, dtype=torch.float64, device="cuda"))
+    torch.cuda.synchronize()
+    grp = fa.FlowFVGroup(sps)
+    ptrs = [[x.data_ptr() for x in xs] for xs in (dus, drs, dts)]
+    grp.compute_residual_device(*ptrs, True, True)
+    torch.cuda.synchronize()
+    before = [x.clone() for x in drs + dts]
+    with pytest.raises(RuntimeError, match="FVHIP_RES_HALO_READY: only the fused"):
+        sps[0].compute_residual_device(ptrs[0][0], ptrs[1][0], ptrs[2][0], True, True, staged=True, halo_ready=True)
+    for x in drs + dts:
+        x.zero_()
+    torch.cuda.synchronize()
+    for sp in sps:
+        sp.profile(True)
+    grp.compute_residual_device(*ptrs, True, True)
+    torch.cuda.synchronize()
+    names = [list(sp.kernel_times()) for sp in sps]
+    after = [x.clone() for x in drs + dts]
+    grp.close()
+    for sp in sps:
+        sp.close()
+    for k, ks in enumerate(names):
+        assert any(x.startswith("k_residual_wls") for x in ks), (k, ks)
+        assert not any(x.startswith("k_sweep") for x in ks), (k, ks)
+    for a, b in zip(before, after):
+        assert torch.equal(a, b)

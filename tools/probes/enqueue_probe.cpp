@@ -1,5 +1,5 @@
 // Host enqueue cost of one partitioned rank's residual step, on one GPU.
-// The RCCL rank step (ctx.hpp residual_fused_overlapped) enqueues: event record + stream wait, the pack,
+// The RCCL rank step (residual.cpp residualOverlapped, one handle) enqueues: event record + stream wait, the pack,
 // ncclGroupStart, one ncclSend/ncclRecv pair per neighbour, ncclGroupEnd, the layer-1 ghost gradients,
 // the interior and the border fused launches, event record + stream wait. RCCL refuses two ranks on one
 // device, so the pairs here go to the rank itself over a 1-rank communicator with the rank's own
