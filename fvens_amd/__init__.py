@@ -130,6 +130,18 @@ def _solve_stats(st, hist):
                 cfl=float(st.cfl), lin_unconverged=int(st.lin_unconverged), lin_worst=float(st.lin_worst)), hist[:n]
 
 
+def _ssprk(call, order, finaltime, maxsteps, cfl, dt, record):
+    """runs one of the fvhip_*ssprk_device entry points: call(config, stats, record pointer or None); returns
+    (stats dict, record rows [steps][6] = t after the step, h, sum area*(rho, rho u, rho v, E); None if not asked)"""
+    c = _ffi.FvUnsteadyConfig(int(order), float(cfl), float(dt), float(finaltime), int(maxsteps))
+    st = _ffi.FvUnsteadyStats()
+    rec = np.zeros((max(int(maxsteps), 1), 6)) if record else None
+    check(call(ctypes.byref(c), ctypes.byref(st), dptr(rec) if record else None))
+    stats = dict(steps=int(st.steps), time=float(st.time), dt_min=float(st.dt_min), dt_max=float(st.dt_max),
+                 cfl_max=float(st.cfl_max))
+    return stats, (rec[:stats["steps"]] if record else None)
+
+
 class UMesh:
     """Reference-indexed mesh built natively (mesh/mesh.hpp accessors as numpy arrays)."""
 
@@ -470,6 +482,13 @@ class FlowFV:
         check(_ffi.lib().fvhip_tvdrk_device(self._h, ctypes.c_void_p(d_u), int(order), float(cfl), float(finaltime),
                                             int(maxsteps), iptr(steps), dptr(t)))
         return int(steps[0]), float(t[0])
+
+    def ssprk_device(self, d_u, order, finaltime, maxsteps, cfl=0.0, dt=0.0, record=False):
+        """time-accurate SSP Runge-Kutta of order 1-3 on the device (fvhip_ssprk_device: stage-state residuals,
+        forward in time, lands on finaltime); one of cfl (h = cfl dtmin) and dt (fixed step). Returns (stats dict:
+        steps, time, dt_min, dt_max, cfl_max; the record rows taken [steps][6], or None without record)"""
+        return _ssprk(lambda c, st, rec: _ffi.lib().fvhip_ssprk_device(self._h, ctypes.c_void_p(d_u), c, st, rec),
+                      order, finaltime, maxsteps, cfl, dt, record)
 
     def steady_backward_euler_device(self, d_u, cfg: ImplicitConfig):
         """SteadyBackwardEulerSolver::solve on the device (aodesolver.cpp:363-638), linear systems by
@@ -833,6 +852,12 @@ class FlowFVGroup:
         check(_ffi.lib().fvhip_group_tvdrk_device(self._g, self._ptrs(d_us), int(order), float(cfl), float(finaltime),
                                                   int(maxsteps), iptr(steps), dptr(t)))
         return int(steps[0]), float(t[0])
+
+    def ssprk_device(self, d_us, order, finaltime, maxsteps, cfl=0.0, dt=0.0, record=False):
+        """FlowFV.ssprk_device over the group: one global time step, the record's sums over all ranks"""
+        ptrs = self._ptrs(d_us)
+        return _ssprk(lambda c, st, rec: _ffi.lib().fvhip_group_ssprk_device(self._g, ptrs, c, st, rec),
+                      order, finaltime, maxsteps, cfl, dt, record)
 
     def steady_backward_euler_device(self, d_us, cfg: ImplicitConfig):
         st = _ffi.FvSolveStats()

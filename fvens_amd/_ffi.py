@@ -54,6 +54,16 @@ class FvSolveStats(ctypes.Structure):
                 ("lin_worst", ctypes.c_double)]
 
 
+class FvUnsteadyConfig(ctypes.Structure):
+    _fields_ = [("order", ctypes.c_int), ("cfl", ctypes.c_double), ("dt", ctypes.c_double),
+                ("finaltime", ctypes.c_double), ("maxsteps", ctypes.c_int)]
+
+
+class FvUnsteadyStats(ctypes.Structure):
+    _fields_ = [("steps", ctypes.c_int), ("time", ctypes.c_double), ("dt_min", ctypes.c_double),
+                ("dt_max", ctypes.c_double), ("cfl_max", ctypes.c_double)]
+
+
 _vpp = ctypes.POINTER(ctypes.c_void_p)
 
 # name -> (restype, argtypes); kept in sync with include/fvhip.h (tests check every symbol)
@@ -114,6 +124,10 @@ _SIGS = {
                                           ctypes.c_double, ctypes.c_int, c_int_p, c_dbl_p]),
     "fvhip_group_tvdrk_device": (ctypes.c_int, [ctypes.c_void_p, _vpp, ctypes.c_int, ctypes.c_double,
                                                 ctypes.c_double, ctypes.c_int, c_int_p, c_dbl_p]),
+    "fvhip_ssprk_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(FvUnsteadyConfig),
+                                          ctypes.POINTER(FvUnsteadyStats), c_dbl_p]),
+    "fvhip_group_ssprk_device": (ctypes.c_int, [ctypes.c_void_p, _vpp, ctypes.POINTER(FvUnsteadyConfig),
+                                                ctypes.POINTER(FvUnsteadyStats), c_dbl_p]),
     "fvhip_steady_backward_euler_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p,
                                                           ctypes.POINTER(FvImplicitConfig),
                                                           ctypes.POINTER(FvSolveStats), c_dbl_p]),

@@ -270,6 +270,30 @@ private:
 	int maxsteps;
 };
 
+/// The time-accurate explicit solver (fvhip_ssprk_device): SSP Runge-Kutta of the stated order with stage-state
+/// residuals, forward in time, landing on finaltime. Constructed like TVDRKSolver_HIP with (temporal order,
+/// physical CFL); fixed_dt > 0 takes that step instead of cfl * dtmin. keep_record: one row per step in `record`
+class SSPRKSolver_HIP
+{
+public:
+	SSPRKSolver_HIP(const FlowFV_HIP* s, int temporal_order, double cfl_num, int max_steps, double fixed_dt = 0.0,
+	                bool keep_record = false)
+		: spatial(s), conf{temporal_order, fixed_dt > 0.0 ? 0.0 : cfl_num, fixed_dt, 0.0, max_steps}, keep(keep_record) { }
+	StatusCode solve(double* d_u, double finaltime) {
+		conf.finaltime = finaltime;
+		record.assign(keep && conf.maxsteps > 0 ? 6*static_cast<size_t>(conf.maxsteps) : 0, 0.0);
+		check(fvhip_ssprk_device(spatial->handle(), d_u, &conf, &stats, keep ? record.data() : nullptr));
+		record.resize(keep ? 6*static_cast<size_t>(stats.steps) : 0);
+		return 0;
+	}
+	fvhip_unsteady_stats stats{};
+	std::vector<double> record;   ///< [steps][6]: t after the step, h, sum area*(rho, rho u, rho v, E)
+private:
+	const FlowFV_HIP* spatial;
+	fvhip_unsteady_config conf;
+	bool keep;
+};
+
 /// Batched InviscidFlux::get_flux / get_jacobian on the device (anumericalflux.hpp:32-45)
 class InviscidFlux_HIP
 {

@@ -284,6 +284,42 @@ int fvhip_tvdrk_device(fvhip_handle h, double* d_u, int order, double cfl, doubl
 int fvhip_group_tvdrk_device(fvhip_group g, double* const* d_u, int order, double cfl, double finaltime, int maxsteps,
                              int* steps, double* time);
 
+/** Time-accurate explicit driver: Shu-Osher SSP Runge-Kutta of temporal order 1-3 with the coefficients of
+ *  initialize_TVDRK_Coeffs (aodesolver.cpp:45-67). It differs from fvhip_tvdrk_device, which restates the
+ *  reference's loop as written, in three ways:
+ *  - stage-state residuals: stage s >= 2 takes the residual at that stage's state. The reference passes the
+ *    step's start state to every stage (:719), and with these coefficients that is forward Euler: first order
+ *    in time whatever `order` says.
+ *  - the sign: compute_residual assembles -r(u) (flow_spatial.cpp:551-559), so du/dt = -r/area is
+ *    u += h/area * residual, as the reference's forward Euler does (:208). Its TVD-RK loop subtracts (:740)
+ *    and so steps backwards in time; fvhip_tvdrk_device keeps that.
+ *  - the final-time landing: a step that would reach or pass finaltime is shortened to h = finaltime - t and
+ *    the time returned is finaltime exactly (the reference overshoots by up to one step).
+ *  Per step h = dt if dt > 0, else cfl * dtmin with dtmin the minimum of the local time steps over all cells
+ *  of all ranks at the step's start state; exactly one of cfl > 0 and dt > 0 must be given. dtmin is read every
+ *  step in both modes: a non-finite one ends the run with "SSP-RK diverged - dtmin is Nan or inf!". The loop
+ *  runs while t < finaltime and fewer than maxsteps steps are taken. */
+typedef struct fvhip_unsteady_config {
+	int order;          /* temporal order 1, 2 or 3 */
+	double cfl;         /* h = cfl * dtmin (0 with a fixed dt) */
+	double dt;          /* fixed step (0 with cfl) */
+	double finaltime;   /* > 0 */
+	int maxsteps;       /* >= 1 */
+} fvhip_unsteady_config;
+typedef struct fvhip_unsteady_stats {
+	int steps;
+	double time;        /* physical time reached: finaltime exactly unless maxsteps ended the run */
+	double dt_min, dt_max;   /* smallest and largest step taken */
+	double cfl_max;     /* largest h / dtmin */
+} fvhip_unsteady_stats;
+/** d_u: device state in internal order, with room for the ghost rows on partitioned and periodic handles.
+ *  record (host, [maxsteps][6], may be NULL): per step the time after it, h, and the sums of area * u over all
+ *  owned cells of all ranks for (rho, rho u, rho v, E), reduced in a fixed order. */
+int fvhip_ssprk_device(fvhip_handle h, double* d_u, const fvhip_unsteady_config* cfg, fvhip_unsteady_stats* stats,
+                       double* record);
+int fvhip_group_ssprk_device(fvhip_group g, double* const* d_u, const fvhip_unsteady_config* cfg,
+                             fvhip_unsteady_stats* stats, double* record);
+
 /** SteadySolverConfig of the main (or starter) solve (aodesolver.hpp, controlparser.cpp:150-206) and
  *  the linear-solver options of the reference's .solverc files */
 typedef struct fvhip_implicit_config {
