@@ -1,7 +1,7 @@
 /** \file blk4.hpp
- * \brief Device helpers on row-major 4x4 fp64 blocks shared by the preconditioner kernels (krylov.hip,
- *   amg.hip): block-vector product, inverse (Gauss-Jordan with pivoting by selects), loads and stores.
- *   Also nblk, the launch-grid size every .hip file uses (jacobian.hip and sweep_device.hpp include
+ * \brief Device helpers on row-major 4x4 fp64 blocks shared by the preconditioner kernels (blockops.hip,
+ *   lines.hip, amg.hip): block-vector product, inverse (Gauss-Jordan with pivoting by selects), loads and stores.
+ *   Also nblk, the launch-grid size every .hip file uses (jacobian.hip, krylov.hip and sweep_device.hpp include
  *   this header for it: it is the one project header light enough for all of them).
  */
 #ifndef FVHIP_BLK4_HPP

@@ -13,6 +13,8 @@
 #include "layout.hpp"
 #include "kernels.hpp"
 #include "jacobian.hpp"
+#include "blockops.hpp"
+#include "lines.hpp"
 #include "mesh.hpp"
 #include "partition.hpp"
 #include "halo.hpp"
@@ -135,9 +137,7 @@ struct fvhip_ctx
 	double mf_eps = 1e-7;
 	const double *mf_u = nullptr, *mf_r = nullptr, *mf_mdt = nullptr;   // device state of the operator
 	double *d_part = nullptr, *d_pm = nullptr;
-	double *d_rn_part = nullptr, *d_rn = nullptr;   // residual-norm reduction of the explicit driver
-	double* d_ustage = nullptr;                      // TVD Runge-Kutta stage state (owned rows)
-	double* d_sspstage = nullptr;                    // SSP Runge-Kutta stage state (owned + ghost rows: a residual's input)
+	double* d_stage = nullptr;                       // Runge-Kutta stage state (owned + ghost rows: SSP-RK's is a residual's input)
 	double* d_ent = nullptr;                        // entropy-error partial sums (fvhip_entropy_error_device)
 	/// work space of the implicit solver (implicit.cpp), allocated on first use
 	struct ImplicitWork {

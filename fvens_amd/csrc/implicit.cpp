@@ -1,7 +1,7 @@
 /** \file implicit.cpp
- * \brief Device-resident pseudo-time solvers over one global system:
- *   SteadyForwardEulerSolver::solve (aodesolver.cpp:135-282) and SteadyBackwardEulerSolver::solve
- *   (aodesolver.cpp:363-638), plus the matrix-free operator over a system.
+ * \brief The device-resident implicit pseudo-time solver over one global system:
+ *   SteadyBackwardEulerSolver::solve (aodesolver.cpp:363-638), its GMRES and the matrix-free operator over a
+ *   system. The explicit drivers are in explicit.cpp.
  *
  * The reference hands each linear system to PETSc (KSPSolve, aodesolver.cpp:483; GMRES with a
  * block-Jacobi/ILU or SOR preconditioner from the .solverc files). Here it is solved on the device
@@ -276,194 +276,6 @@ static void backwardEuler(System& S, const std::vector<double*>& us, const fvhip
 	st->lin_worst = linworst;
 }
 
-/// SteadyForwardEulerSolver::solve (aodesolver.cpp:135-282): u += cflinit dtm/area r (the ramped
-/// CFL is only reported by the reference, :194, :208)
-static void forwardEuler(System& S, const std::vector<double*>& us, double cfl, double tol, int maxiter,
-                         int* steps, double* resratio, double* hist)
-{
-	S.each([&](size_t, fvhip_ctx* h) { h->ensureReductions(); });
-	double resi = 1.0, initres = 1.0;
-	int step = 0;
-	while(resi/initres > tol && step < maxiter) {
-		S.residual(us);                                                                           // :180-189
-		S.each([&](size_t i, fvhip_ctx* h) {
-			launch_fe_update(h->L.ncell, h->d_r, h->d_dtm, h->M.area, cfl, us[i], h->stream);   // :204-209
-			launch_energy_sumsq(h->L.ncell, h->d_r, h->M.area, h->iw.part, h->iw.red, h->stream);
-			HC(hipGetLastError());
-		});
-		resi = std::sqrt(S.allsum(1, false)[0]);                                                  // :214-230
-		if(step == 0) initres = resi;
-		if(hist) hist[step] = resi;
-		step++;
-		if(!std::isfinite(resi))
-			throw std::runtime_error("Steady forward Euler diverged - residual is Nan or inf!");  // :250-251
-	}
-	if(steps) *steps = step;
-	if(resratio) *resratio = resi/initres;
-}
-
-/// TVDRKSolver::solve (aodesolver.cpp:669-758) on the device, restated as written: ustage = u once
-/// before the time loop (:701-704); per step, every stage's residual is computed at u -- the step's
-/// start state, since the reference passes uvec, not the stage state, to compute_residual (:719) --
-/// dtmin = min over cells of the first stage's local time steps (:722-728; across ranks the global
-/// minimum, so a partitioned run takes the 1-GPU steps, where the reference's ranks would each take
-/// their own), ustage = c0 u + c1 ustage - c2 dtmin cfl / area r (:735-744), then u = ustage and
-/// time += dtmin cfl (:747-757), while time <= finaltime - 1e-12 (A_SMALL_NUMBER). The stages' residuals
-/// are the same bits (same input, deterministic kernels), so one residual per step is computed and
-/// reused. maxsteps caps the loop (the reference has no cap).
-static void tvdrk(System& S, const std::vector<double*>& us, int order, double cfl, double finaltime, int maxsteps,
-                  int* steps, double* time_out)
-{
-	static const double coef[3][3][3] = {                                       // initialize_TVDRK_Coeffs :45-67
-		{{1.0, 0.0, 1.0}, {0, 0, 0}, {0, 0, 0}},
-		{{1.0, 0.0, 1.0}, {0.5, 0.5, 0.5}, {0, 0, 0}},
-		{{1.0, 0.0, 1.0}, {0.75, 0.25, 0.25}, {0.3333333333333333, 0.6666666666666667, 0.6666666666666667}}};
-	if(order < 1 || order > 3) throw std::invalid_argument("TVD RK: temporal order must be 1, 2 or 3");
-	if(maxsteps < 1) throw std::invalid_argument("TVD RK: maxsteps must be >= 1");
-	const double (*tc)[3] = coef[order-1];
-	S.each([&](size_t i, fvhip_ctx* h) {
-		h->ensureReductions();
-		if(!h->d_ustage) h->d_ustage = dalloc(4*static_cast<size_t>(std::max(h->L.ncell, 1)), h->owned);
-		HC(hipMemcpyAsync(h->d_ustage, us[i], sizeof(double)*4*static_cast<size_t>(h->L.ncell), hipMemcpyDeviceToDevice,
-		                  h->stream));
-	});
-	int step = 0;
-	double time = 0;
-	while(time <= finaltime - 1e-12 && step < maxsteps) {
-		S.residual(us);                                                             // :712-719 (zeroed, -r(u))
-		S.each([&](size_t, fvhip_ctx* h) {
-			launch_min(h->L.ncell, h->d_dtm, h->iw.part, h->iw.red, h->stream);
-			if(h->comm) NC(ncclAllReduce(h->iw.red, h->iw.red, 1, ncclDouble, ncclMin, h->comm, h->stream));
-			HC(hipMemcpyAsync(h->iw.h_red, h->iw.red, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-		});
-		double dtmin = INFINITY;
-		S.each([&](size_t, fvhip_ctx* h) { HC(hipStreamSynchronize(h->stream)); dtmin = std::min(dtmin, h->iw.h_red[0]); });
-		if(!std::isfinite(dtmin)) throw std::runtime_error("TVDRK solver diverged - dtmin is Nan or inf!");   // :730-731
-		for(int s = 0; s < order; s++) {
-			const double sc = tc[s][2]*dtmin*cfl;
-			S.each([&](size_t i, fvhip_ctx* h) {
-				launch_tvdrk_stage(h->L.ncell, tc[s][0], tc[s][1], sc, h->M.area, h->d_r, us[i], h->d_ustage, h->stream);
-			});
-		}
-		S.each([&](size_t i, fvhip_ctx* h) {
-			HC(hipMemcpyAsync(us[i], h->d_ustage, sizeof(double)*4*static_cast<size_t>(h->L.ncell), hipMemcpyDeviceToDevice,
-			                  h->stream));
-			HC(hipGetLastError());
-		});
-		step++;
-		time += dtmin*cfl;
-	}
-	if(steps) *steps = step;
-	if(time_out) *time_out = time;
-}
-
-/// the time-accurate driver's arguments, refused by name before any handle or device is touched
-static void checkUnsteady(const fvhip_unsteady_config* c, const fvhip_unsteady_stats* st)
-{
-	need(c, "config");
-	need(st, "stats");
-	if(c->order < 1 || c->order > 3) throw std::invalid_argument("SSP-RK: temporal order must be 1, 2 or 3");
-	if(c->maxsteps < 1) throw std::invalid_argument("SSP-RK: maxsteps must be >= 1");
-	if(!(c->finaltime > 0.0)) throw std::invalid_argument("SSP-RK: finaltime must be > 0");
-	if((c->cfl > 0.0) == (c->dt > 0.0))
-		throw std::invalid_argument("SSP-RK: exactly one of cfl > 0 and dt > 0 must be given");
-}
-
-/// Time-accurate Shu-Osher SSP Runge-Kutta of order 1-3 (the coefficients of initialize_TVDRK_Coeffs,
-/// aodesolver.cpp:45-67). Unlike tvdrk above, which keeps the reference's loop as written, every stage's residual
-/// is taken at that stage's state (tvdrk: at the step's start state, which makes every order forward Euler), the
-/// update adds the assembled residual (d_r holds -r(u), so u' = -r/area is u += h/area d_r; tvdrk keeps the
-/// reference's minus and runs backwards in time) and the last step is shortened to land on finaltime exactly.
-/// Per step: d_r, d_dtm at u; dtmin = global minimum of d_dtm (read every step: the divergence check and
-/// cfl_max = max h/dtmin); h = dt if given, else cfl dtmin, cut to finaltime - t when t + h reaches finaltime;
-/// stage s: ustage = (c0 u + c1 ustage) + ((c2 h)/area) d_r with d_r at ustage for s >= 2; the last stage
-/// writes u. The stage state is a residual's input (its ghost rows get filled), hence d_sspstage with ghost rows.
-/// record [maxsteps][6] (host, may be null): t after the step, h, and sum area u of the four conserved variables.
-static void ssprk(System& S, const std::vector<double*>& us, const fvhip_unsteady_config& c, fvhip_unsteady_stats* st,
-                  double* record)
-{
-	static const double coef[3][3][3] = {                                       // initialize_TVDRK_Coeffs :45-67
-		{{1.0, 0.0, 1.0}, {0, 0, 0}, {0, 0, 0}},
-		{{1.0, 0.0, 1.0}, {0.5, 0.5, 0.5}, {0, 0, 0}},
-		{{1.0, 0.0, 1.0}, {0.75, 0.25, 0.25}, {0.3333333333333333, 0.6666666666666667, 0.6666666666666667}}};
-	const double (*tc)[3] = coef[c.order-1];
-	std::vector<double*> ust;
-	S.each([&](size_t, fvhip_ctx* h) {
-		h->ensureReductions();
-		if(!h->d_sspstage) h->d_sspstage = dalloc(4*static_cast<size_t>(std::max(h->ntotal(), 1)), h->owned);
-		ust.push_back(h->d_sspstage);
-	});
-	int step = 0;
-	double time = 0, hmin = INFINITY, hmax = 0, cflmax = 0;
-	while(time < c.finaltime && step < c.maxsteps) {
-		S.residual(us);                                                             // -r(u^n), local time steps
-		S.each([&](size_t, fvhip_ctx* h) {
-			launch_min(h->L.ncell, h->d_dtm, h->iw.part, h->iw.red, h->stream);
-			if(h->comm) NC(ncclAllReduce(h->iw.red, h->iw.red, 1, ncclDouble, ncclMin, h->comm, h->stream));
-			HC(hipMemcpyAsync(h->iw.h_red, h->iw.red, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-		});
-		double dtmin = INFINITY;
-		S.each([&](size_t, fvhip_ctx* h) { HC(hipStreamSynchronize(h->stream)); dtmin = std::min(dtmin, h->iw.h_red[0]); });
-		if(!std::isfinite(dtmin)) throw std::runtime_error("SSP-RK diverged - dtmin is Nan or inf!");
-		double dt = c.dt > 0.0 ? c.dt : c.cfl*dtmin;
-		const bool last = time + dt >= c.finaltime;
-		if(last) dt = c.finaltime - time;
-		for(int s = 0; s < c.order; s++) {
-			if(s > 0) S.residual(ust);                                              // -r at the stage state
-			const double sc = tc[s][2]*dt;
-			S.each([&](size_t i, fvhip_ctx* h) {
-				// the first stage has c1 = 0 and reads u in ustage's place; the last writes u
-				launch_ssprk_stage(h->L.ncell, tc[s][0], tc[s][1], sc, h->M.area, h->d_r, us[i], s == 0 ? us[i] : ust[i],
-				                   s == c.order-1 ? us[i] : ust[i], h->stream);
-				HC(hipGetLastError());
-			});
-		}
-		time = last ? c.finaltime : time + dt;
-		hmin = std::min(hmin, dt); hmax = std::max(hmax, dt); cflmax = std::max(cflmax, dt/dtmin);
-		if(record) {
-			S.each([&](size_t i, fvhip_ctx* h) {
-				launch_conserved(h->L.ncell, us[i], h->M.area, h->iw.part, h->iw.red, h->stream);
-				HC(hipGetLastError());
-			});
-			const std::vector<double> sums = S.allsum(4, false);
-			double* row = record + 6*static_cast<size_t>(step);
-			row[0] = time; row[1] = dt;
-			std::copy(sums.begin(), sums.end(), row + 2);
-		}
-		step++;
-	}
-	st->steps = step;
-	st->time = time;
-	st->dt_min = hmin; st->dt_max = hmax; st->cfl_max = cflmax;
-}
-
-typedef std::vector<double*> States;
-
-/// a stepper's entry point on one handle / on a group: the arguments checked (have: its other pointers are there),
-/// the system made, `step(S, states)` run and waited for
-template <typename F> static int onHandle(fvhip_handle h, double* d_u, bool have, F&& step)
-{
-	return guard([&] {
-		need(h, "handle");
-		need(d_u, "u");
-		if(!have) throw std::invalid_argument("null argument");
-		System S = single(h);
-		step(S, States{d_u});
-		S.sync();
-	});
-}
-template <typename F> static int onGroup(fvhip_group g, double* const* d_u, bool have, F&& step)
-{
-	return guard([&] {
-		need(g, "group");
-		needEach(d_u, g->hs.size(), "u");
-		if(!have) throw std::invalid_argument("null argument");
-		System S = ofGroup(g);
-		step(S, States(d_u, d_u + S.size()));
-		S.sync();
-	});
-}
-
 }
 
 using namespace fvhip_detail;
@@ -480,44 +292,6 @@ int fvhip_group_steady_backward_euler_device(fvhip_group g, double* const* d_u, 
                                              fvhip_solve_stats* stats, double* reshistory)
 {
 	return onGroup(g, d_u, cfg && stats, [&](System& S, const States& us) { backwardEuler(S, us, *cfg, stats, reshistory); });
-}
-
-int fvhip_steady_forward_euler_device(fvhip_handle h, double* d_u, double cfl, double tol, int maxiter,
-                                      int* steps, double* resratio, double* reshistory)
-{
-	return onHandle(h, d_u, true, [&](System& S, const States& us) { forwardEuler(S, us, cfl, tol, maxiter, steps, resratio, reshistory); });
-}
-
-int fvhip_group_steady_forward_euler_device(fvhip_group g, double* const* d_u, double cfl, double tol, int maxiter,
-                                            int* steps, double* resratio, double* reshistory)
-{
-	return onGroup(g, d_u, true, [&](System& S, const States& us) { forwardEuler(S, us, cfl, tol, maxiter, steps, resratio, reshistory); });
-}
-
-int fvhip_tvdrk_device(fvhip_handle h, double* d_u, int order, double cfl, double finaltime, int maxsteps,
-                       int* steps, double* time)
-{
-	return onHandle(h, d_u, true, [&](System& S, const States& us) { tvdrk(S, us, order, cfl, finaltime, maxsteps, steps, time); });
-}
-
-int fvhip_group_tvdrk_device(fvhip_group g, double* const* d_u, int order, double cfl, double finaltime, int maxsteps,
-                             int* steps, double* time)
-{
-	return onGroup(g, d_u, true, [&](System& S, const States& us) { tvdrk(S, us, order, cfl, finaltime, maxsteps, steps, time); });
-}
-
-int fvhip_ssprk_device(fvhip_handle h, double* d_u, const fvhip_unsteady_config* cfg, fvhip_unsteady_stats* stats,
-                       double* record)
-{
-	if(guard([&] { checkUnsteady(cfg, stats); })) return 1;
-	return onHandle(h, d_u, true, [&](System& S, const States& us) { ssprk(S, us, *cfg, stats, record); });
-}
-
-int fvhip_group_ssprk_device(fvhip_group g, double* const* d_u, const fvhip_unsteady_config* cfg,
-                             fvhip_unsteady_stats* stats, double* record)
-{
-	if(guard([&] { checkUnsteady(cfg, stats); })) return 1;
-	return onGroup(g, d_u, true, [&](System& S, const States& us) { ssprk(S, us, *cfg, stats, record); });
 }
 
 int fvhip_gmres_blocks_device(fvhip_handle h, const double* d_diag, const double* d_lower, const double* d_upper,

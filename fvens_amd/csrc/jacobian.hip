@@ -1,11 +1,10 @@
 /** \file jacobian.hip
- * \brief Analytic first-order Jacobian assembly, pseudo-time diagonal, block operator apply and the
- *   matrix-free finite-difference operator on MI355X.
+ * \brief Analytic first-order Jacobian assembly and the pseudo-time diagonal on MI355X (the block operator on
+ *   the assembled blocks: blockops.hip; the matrix-free operator's vector kernels: krylov.hip).
  *
  * Replaces Spatial::assemble_jacobian (aspatial.cpp:242-340) with
- * FlowFV::compute_local_jacobian_interior/_boundary (flow_spatial.cpp:818-875),
- * SteadyBackwardEulerSolver::addPseudoTimeTerm (aodesolver.cpp:300-329) and
- * MatrixFreeSpatialJacobian::apply (alinalg.cpp:142-233).
+ * FlowFV::compute_local_jacobian_interior/_boundary (flow_spatial.cpp:818-875) and
+ * SteadyBackwardEulerSolver::addPseudoTimeTerm (aodesolver.cpp:300-329).
  *
  * Storage is face-based, which is what the reference's assembly produces block by block:
  *   lower[fi], upper[fi] (interior face fi = f - nbface, reference order): A[R][L] += L, A[L][R] += U;
@@ -328,370 +327,6 @@ void k_pseudo_time(int ncell, const double* __restrict__ area, double cfl, doubl
 		for(int j = 0; j < 4; j++) d[i*4+j] += m*(i == j ? 1.0 : 0.0);
 }
 
-// -------------------------------------------------------------------------------------------------
-// y = A x with the face-based blocks; per cell: diag first, then faces in ascending reference order
-// -------------------------------------------------------------------------------------------------
-/// s[i] = sum_k B[i][k] x[k] for a row-major 4x4 block, rows read as double4 (k ascending)
-__device__ __forceinline__ void blk_row_dots(const double* __restrict__ B, const double4 x, double (&s)[4])
-{
-	const double4* b4 = reinterpret_cast<const double4*>(B);
-#pragma unroll
-	for(int i = 0; i < 4; i++) {
-		const double4 r = b4[i];
-		s[i] = r.x*x.x + r.y*x.y + r.z*x.z + r.w*x.w;
-	}
-}
-/// the same for an fp32 block (entries widened to fp64, fp64 arithmetic)
-__device__ __forceinline__ void blk_row_dots(const float* __restrict__ B, const double4 x, double (&s)[4])
-{
-	const float4* b4 = reinterpret_cast<const float4*>(B);
-#pragma unroll
-	for(int i = 0; i < 4; i++) {
-		const float4 r = b4[i];
-		s[i] = static_cast<double>(r.x)*x.x + static_cast<double>(r.y)*x.y + static_cast<double>(r.z)*x.z
-		     + static_cast<double>(r.w)*x.w;
-	}
-}
-
-__global__ __launch_bounds__(256)
-void k_block_apply(JacMesh J, const double* __restrict__ diag, const double* __restrict__ lower,
-                   const double* __restrict__ upper, const double* __restrict__ x, double* __restrict__ y)
-{
-	const int c = blockIdx.x*blockDim.x + threadIdx.x;
-	if(c >= J.ncell) return;
-	const double4* x4 = reinterpret_cast<const double4*>(x);
-	double acc[4];
-	blk_row_dots(diag + 16*static_cast<size_t>(c), x4[c], acc);
-	const int4 fc = J.cell_rfaces[c];
-	const int4 nb = J.cell_nbr_fo[c];
-	const int codes[4] = {fc.x, fc.y, fc.z, fc.w};
-	const int nbrs[4] = {nb.x, nb.y, nb.z, nb.w};
-#pragma unroll
-	for(int j = 0; j < 4; j++) {
-		const int code = codes[j];
-		if(code < 0) continue;
-		const int f = code >> 1;
-		if(f < J.nbface) continue;
-		const double* B = ((code & 1) ? lower : upper) + 16*static_cast<size_t>(f - J.nbface);
-		double s[4];
-		blk_row_dots(B, x4[nbrs[j]], s);
-#pragma unroll
-		for(int i = 0; i < 4; i++) acc[i] += s[i];
-	}
-	reinterpret_cast<double4*>(y)[c] = make_double4(acc[0], acc[1], acc[2], acc[3]);
-}
-
-/// k_block_apply with four lanes per cell, lane i forming y[c][i]: the same row dot products in the same
-/// order (diagonal block first, then the faces ascending), so bitwise the same y; each block is read as four
-/// consecutive 32-byte rows by four consecutive lanes, and y is written as one 32-byte row per cell
-__global__ __launch_bounds__(256)
-void k_block_apply_rows(JacMesh J, const double* __restrict__ diag, const double* __restrict__ lower,
-                        const double* __restrict__ upper, const double* __restrict__ x, double* __restrict__ y)
-{
-	const long long g = static_cast<long long>(blockIdx.x)*blockDim.x + threadIdx.x;
-	const int c = static_cast<int>(g >> 2), i = static_cast<int>(g & 3);
-	if(c >= J.ncell) return;
-	const double4* x4 = reinterpret_cast<const double4*>(x);
-	const int4 fc = J.cell_rfaces[c];
-	const int4 nb = J.cell_nbr_fo[c];
-	const int codes[4] = {fc.x, fc.y, fc.z, fc.w};
-	const int nbrs[4] = {nb.x, nb.y, nb.z, nb.w};
-	double4 r = reinterpret_cast<const double4*>(diag + 16*static_cast<size_t>(c))[i];
-	double4 xv = x4[c];
-	double acc = r.x*xv.x + r.y*xv.y + r.z*xv.z + r.w*xv.w;
-#pragma unroll
-	for(int j = 0; j < 4; j++) {
-		const int code = codes[j];
-		if(code < 0) continue;
-		const int f = code >> 1;
-		if(f < J.nbface) continue;
-		const double* B = ((code & 1) ? lower : upper) + 16*static_cast<size_t>(f - J.nbface);
-		r = reinterpret_cast<const double4*>(B)[i];
-		xv = x4[nbrs[j]];
-		acc += r.x*xv.x + r.y*xv.y + r.z*xv.z + r.w*xv.w;
-	}
-	y[4*static_cast<size_t>(c) + i] = acc;
-}
-
-/// One block-Jacobi sweep fused into one pass: zout = D^-1 (v - sum_faces B zin[nbr]), the
-/// off-diagonal half of k_block_apply followed by the diagonal solve (zin needs its ghost rows).
-/// Same iterate as zin + D^-1 (v - A zin) up to rounding, without reading D or writing A zin.
-template <typename T>
-__global__ __launch_bounds__(256)
-void k_bjac_sweep(JacMesh J, const T* __restrict__ dinv, const T* __restrict__ lower,
-                  const T* __restrict__ upper, const double* __restrict__ v, const double* __restrict__ zin,
-                  double* __restrict__ zout)
-{
-	const int c = blockIdx.x*blockDim.x + threadIdx.x;
-	if(c >= J.ncell) return;
-	const double4* z4 = reinterpret_cast<const double4*>(zin);
-	const double4 vc = reinterpret_cast<const double4*>(v)[c];
-	double acc[4] = {vc.x, vc.y, vc.z, vc.w};
-	const int4 fc = J.cell_rfaces[c];
-	const int4 nb = J.cell_nbr_fo[c];
-	const int codes[4] = {fc.x, fc.y, fc.z, fc.w};
-	const int nbrs[4] = {nb.x, nb.y, nb.z, nb.w};
-#pragma unroll
-	for(int j = 0; j < 4; j++) {
-		const int code = codes[j];
-		if(code < 0) continue;
-		const int f = code >> 1;
-		if(f < J.nbface) continue;
-		const T* B = ((code & 1) ? lower : upper) + 16*static_cast<size_t>(f - J.nbface);
-		double s[4];
-		blk_row_dots(B, z4[nbrs[j]], s);
-#pragma unroll
-		for(int i = 0; i < 4; i++) acc[i] -= s[i];
-	}
-	double o[4];
-	blk_row_dots(dinv + 16*static_cast<size_t>(c), make_double4(acc[0], acc[1], acc[2], acc[3]), o);
-	reinterpret_cast<double4*>(zout)[c] = make_double4(o[0], o[1], o[2], o[3]);
-}
-
-/// row i of a row-major 4x4 block dotted with x, as blk_row_dots forms it (k ascending)
-__device__ __forceinline__ double blk_row_dot(const double* __restrict__ B, int i, const double4 x)
-{
-	const double4 r = reinterpret_cast<const double4*>(B)[i];
-	return r.x*x.x + r.y*x.y + r.z*x.z + r.w*x.w;
-}
-__device__ __forceinline__ double blk_row_dot(const float* __restrict__ B, int i, const double4 x)
-{
-	const float4 r = reinterpret_cast<const float4*>(B)[i];
-	return static_cast<double>(r.x)*x.x + static_cast<double>(r.y)*x.y + static_cast<double>(r.z)*x.z
-	     + static_cast<double>(r.w)*x.w;
-}
-/// t = v - A x in one pass (the multigrid's finest residuals): k_block_apply_rows' row sum, subtracted from v;
-/// T = float: the blocks stored in fp32 (prec_single: the preconditioner's copy), the arithmetic in fp64
-template <typename T>
-__global__ __launch_bounds__(256)
-void k_block_residual_rows(JacMesh J, const T* __restrict__ diag, const T* __restrict__ lower,
-                           const T* __restrict__ upper, const double* __restrict__ x, const double* __restrict__ v,
-                           double* __restrict__ t)
-{
-	const long long g = static_cast<long long>(blockIdx.x)*blockDim.x + threadIdx.x;
-	const int c = static_cast<int>(g >> 2), i = static_cast<int>(g & 3);
-	if(c >= J.ncell) return;
-	const double4* x4 = reinterpret_cast<const double4*>(x);
-	const int4 fc = J.cell_rfaces[c];
-	const int4 nb = J.cell_nbr_fo[c];
-	const int codes[4] = {fc.x, fc.y, fc.z, fc.w};
-	const int nbrs[4] = {nb.x, nb.y, nb.z, nb.w};
-	double acc = blk_row_dot(diag + 16*static_cast<size_t>(c), i, x4[c]);
-#pragma unroll
-	for(int j = 0; j < 4; j++) {
-		const int code = codes[j];
-		if(code < 0) continue;
-		const int f = code >> 1;
-		if(f < J.nbface) continue;
-		const T* B = ((code & 1) ? lower : upper) + 16*static_cast<size_t>(f - J.nbface);
-		acc += blk_row_dot(B, i, x4[nbrs[j]]);
-	}
-	t[4*static_cast<size_t>(c) + i] = v[4*static_cast<size_t>(c) + i] - acc;
-}
-
-/// k_bjac_sweep with four lanes per cell, lane i forming row i (coalesced block rows, as k_block_apply_rows):
-/// the same row sums in the same order, the four sums exchanged within the cell's lanes for the product
-/// with D^-1, so bitwise k_bjac_sweep's z
-template <typename T>
-__global__ __launch_bounds__(256)
-void k_bjac_sweep_rows(JacMesh J, const T* __restrict__ dinv, const T* __restrict__ lower,
-                       const T* __restrict__ upper, const double* __restrict__ v, const double* __restrict__ zin,
-                       double* __restrict__ zout)
-{
-	const long long g = static_cast<long long>(blockIdx.x)*blockDim.x + threadIdx.x;
-	const int c = static_cast<int>(g >> 2), i = static_cast<int>(g & 3);
-	const bool live = c < J.ncell;
-	const int cc = live ? c : J.ncell - 1;          // lanes past the end compute a copy and store nothing
-	const double4* z4 = reinterpret_cast<const double4*>(zin);
-	double acc = v[4*static_cast<size_t>(cc) + i];
-	const int4 fc = J.cell_rfaces[cc];
-	const int4 nb = J.cell_nbr_fo[cc];
-	const int codes[4] = {fc.x, fc.y, fc.z, fc.w};
-	const int nbrs[4] = {nb.x, nb.y, nb.z, nb.w};
-#pragma unroll
-	for(int j = 0; j < 4; j++) {
-		const int code = codes[j];
-		if(code < 0) continue;
-		const int f = code >> 1;
-		if(f < J.nbface) continue;
-		const T* B = ((code & 1) ? lower : upper) + 16*static_cast<size_t>(f - J.nbface);
-		acc -= blk_row_dot(B, i, z4[nbrs[j]]);
-	}
-	// the cell's four row sums to every lane of the cell (all 64 lanes of the wave take part)
-	const double4 t = make_double4(__shfl(acc, 0, 4), __shfl(acc, 1, 4), __shfl(acc, 2, 4), __shfl(acc, 3, 4));
-	const double o = blk_row_dot(dinv + 16*static_cast<size_t>(cc), i, t);
-	if(live) zout[4*static_cast<size_t>(c) + i] = o;
-}
-
-/// One sweep of a triangular solve of the sweep-based block ILU(0)/SGS (ilu_order, ilu_apply_sweeps), out of
-/// place, four lanes per cell as k_bjac_sweep_rows (row dots in face-slot order, the four sums shared within
-/// the cell's lanes, lanes past the end compute a copy and store nothing). Owned neighbour k of cell i is lower
-/// if rank[k] < rank[i], upper if rank[k] > rank[i] (rank == nullptr: the internal order); ghost neighbours
-/// are skipped (block-Jacobi across ranks).
-///   UPPER = false, the forward solve of (Dt + L) y = v:    zout_i = Dt_i^-1 (w_i - sum_{lower k} A_ik zin_k),  w = v
-///   UPPER = true, the backward solve of (I + Dt^-1 U) z = y:  zout_i = w_i - Dt_i^-1 sum_{upper j} A_ij zin_j,  w = y
-template <typename T, bool UPPER>
-__global__ __launch_bounds__(256)
-void k_ilu_sweep_solve(JacMesh J, const int* __restrict__ rank, const T* __restrict__ dinv, const T* __restrict__ lower,
-                       const T* __restrict__ upper, const double* __restrict__ w, const double* __restrict__ zin,
-                       double* __restrict__ zout)
-{
-	const long long g = static_cast<long long>(blockIdx.x)*blockDim.x + threadIdx.x;
-	const int c = static_cast<int>(g >> 2), i = static_cast<int>(g & 3);
-	const bool live = c < J.ncell;
-	const int cc = live ? c : J.ncell - 1;
-	const double4* z4 = reinterpret_cast<const double4*>(zin);
-	const double wi = w[4*static_cast<size_t>(cc) + i];
-	double acc = UPPER ? 0.0 : wi;
-	const int4 fc = J.cell_rfaces[cc];
-	const int4 nb = J.cell_nbr_fo[cc];
-	const int codes[4] = {fc.x, fc.y, fc.z, fc.w};
-	const int nbrs[4] = {nb.x, nb.y, nb.z, nb.w};
-	const int rc = rank ? rank[cc] : cc;
-#pragma unroll
-	for(int j = 0; j < 4; j++) {
-		const int code = codes[j], k = nbrs[j];
-		if(code < 0) continue;
-		const int f = code >> 1;
-		if(f < J.nbface || k < 0 || k >= J.ncell) continue;
-		const int rk = rank ? rank[k] : k;
-		if(UPPER ? rk <= rc : rk >= rc) continue;
-		const T* B = ((code & 1) ? lower : upper) + 16*static_cast<size_t>(f - J.nbface);
-		acc -= blk_row_dot(B, i, z4[k]);
-	}
-	const double4 t = make_double4(__shfl(acc, 0, 4), __shfl(acc, 1, 4), __shfl(acc, 2, 4), __shfl(acc, 3, 4));
-	const double d = blk_row_dot(dinv + 16*static_cast<size_t>(cc), i, t);
-	if(live) zout[4*static_cast<size_t>(c) + i] = UPPER ? wi + d : d;
-}
-
-/// One colour of a multicolour block Gauss-Seidel sweep, in place: z_c = D^-1 (v - sum_faces B z[nbr])
-/// for the listed cells, which share no face, so every neighbour value read is either from an
-/// earlier colour of this sweep or from the previous sweep (ghost rows: from the last exchange).
-template <typename T>
-__global__ __launch_bounds__(256)
-void k_bgs_colour(JacMesh J, const T* __restrict__ dinv, const T* __restrict__ lower, const T* __restrict__ upper,
-                  const double* __restrict__ v, double* z, const int* __restrict__ cells, int n)
-{
-	const int i = blockIdx.x*blockDim.x + threadIdx.x;
-	if(i >= n) return;
-	const int c = cells[i];
-	const double4* z4 = reinterpret_cast<const double4*>(z);
-	const double4 vc = reinterpret_cast<const double4*>(v)[c];
-	double acc[4] = {vc.x, vc.y, vc.z, vc.w};
-	const int4 fc = J.cell_rfaces[c];
-	const int4 nb = J.cell_nbr_fo[c];
-	const int codes[4] = {fc.x, fc.y, fc.z, fc.w};
-	const int nbrs[4] = {nb.x, nb.y, nb.z, nb.w};
-#pragma unroll
-	for(int j = 0; j < 4; j++) {
-		const int code = codes[j];
-		if(code < 0) continue;
-		const int f = code >> 1;
-		if(f < J.nbface) continue;
-		const T* B = ((code & 1) ? lower : upper) + 16*static_cast<size_t>(f - J.nbface);
-		double s[4];
-		blk_row_dots(B, z4[nbrs[j]], s);
-#pragma unroll
-		for(int k = 0; k < 4; k++) acc[k] -= s[k];
-	}
-	double o[4];
-	blk_row_dots(dinv + 16*static_cast<size_t>(c), make_double4(acc[0], acc[1], acc[2], acc[3]), o);
-	reinterpret_cast<double4*>(z)[c] = make_double4(o[0], o[1], o[2], o[3]);
-}
-
-/// k_bgs_colour with four lanes per cell (k_bjac_sweep_rows' arithmetic, in place): bitwise k_bgs_colour's z.
-/// Every lane of the cell reads its neighbours' rows before any lane writes the cell (cells of a colour
-/// share no face, so no neighbour is written by this launch)
-template <typename T>
-__global__ __launch_bounds__(256)
-void k_bgs_colour_rows(JacMesh J, const T* __restrict__ dinv, const T* __restrict__ lower, const T* __restrict__ upper,
-                       const double* __restrict__ v, double* z, const int* __restrict__ cells, int n)
-{
-	const long long g = static_cast<long long>(blockIdx.x)*blockDim.x + threadIdx.x;
-	const int k = static_cast<int>(g >> 2), i = static_cast<int>(g & 3);
-	const bool live = k < n;
-	const int c = cells[live ? k : n - 1];
-	const double4* z4 = reinterpret_cast<const double4*>(z);
-	double acc = v[4*static_cast<size_t>(c) + i];
-	const int4 fc = J.cell_rfaces[c];
-	const int4 nb = J.cell_nbr_fo[c];
-	const int codes[4] = {fc.x, fc.y, fc.z, fc.w};
-	const int nbrs[4] = {nb.x, nb.y, nb.z, nb.w};
-#pragma unroll
-	for(int j = 0; j < 4; j++) {
-		const int code = codes[j];
-		if(code < 0) continue;
-		const int f = code >> 1;
-		if(f < J.nbface) continue;
-		const T* B = ((code & 1) ? lower : upper) + 16*static_cast<size_t>(f - J.nbface);
-		acc -= blk_row_dot(B, i, z4[nbrs[j]]);
-	}
-	const double4 t = make_double4(__shfl(acc, 0, 4), __shfl(acc, 1, 4), __shfl(acc, 2, 4), __shfl(acc, 3, 4));
-	const double o = blk_row_dot(dinv + 16*static_cast<size_t>(c), i, t);
-	if(live) z[4*static_cast<size_t>(c) + i] = o;
-}
-
-// -------------------------------------------------------------------------------------------------
-// matrix-free pieces
-// -------------------------------------------------------------------------------------------------
-constexpr int RED_BLOCKS = 1024;
-
-/// deterministic two-stage sum of squares: fixed partition, fixed tree
-__global__ __launch_bounds__(256)
-void k_sumsq_partial(long long n, const double* __restrict__ x, double* __restrict__ part)
-{
-	__shared__ double s[256];
-	double acc = 0;
-	for(long long i = blockIdx.x*256LL + threadIdx.x; i < n; i += 256LL*gridDim.x) acc += x[i]*x[i];
-	s[threadIdx.x] = acc;
-	__syncthreads();
-	for(int w = 128; w > 0; w >>= 1) {
-		if(threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
-		__syncthreads();
-	}
-	if(threadIdx.x == 0) part[blockIdx.x] = s[0];
-}
-
-/// pertmag = eps / sqrt(sum(part))
-__global__ __launch_bounds__(256)
-void k_pertmag(int np, const double* __restrict__ part, double eps, double* __restrict__ out)
-{
-	__shared__ double s[256];
-	double acc = 0;
-	for(int i = threadIdx.x; i < np; i += 256) acc += part[i];
-	s[threadIdx.x] = acc;
-	__syncthreads();
-	for(int w = 128; w > 0; w >>= 1) {
-		if(threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
-		__syncthreads();
-	}
-	if(threadIdx.x == 0) { out[0] = sqrt(s[0]); out[1] = eps/out[0]; }
-}
-
-__global__ __launch_bounds__(256)
-void k_mf_perturb(long long n, const double* __restrict__ u, const double* __restrict__ x,
-                  const double* __restrict__ pm, double* __restrict__ aux)
-{
-	const long long i = blockIdx.x*256LL + threadIdx.x;
-	if(i >= n) return;
-	aux[i] = u[i] + pm[1]*x[i];
-}
-
-__global__ __launch_bounds__(256)
-void k_mf_combine(int ncell, const double* __restrict__ mdt, const double* __restrict__ x,
-                  const double* __restrict__ yg, const double* __restrict__ res,
-                  const double* __restrict__ pm, double* __restrict__ y)
-{
-	const int c = blockIdx.x*256 + threadIdx.x;
-	if(c >= ncell) return;
-	const double pert = pm[1], d = mdt[c];
-	// one 32-byte row per vector and cell; each entry mdt x + (-yg + res)/pert as before
-	const double4 xv = reinterpret_cast<const double4*>(x)[c], gv = reinterpret_cast<const double4*>(yg)[c];
-	const double4 rv = reinterpret_cast<const double4*>(res)[c];
-	reinterpret_cast<double4*>(y)[c] = make_double4(d*xv.x + (-gv.x + rv.x)/pert, d*xv.y + (-gv.y + rv.y)/pert,
-	                                                d*xv.z + (-gv.z + rv.z)/pert, d*xv.w + (-gv.w + rv.w)/pert);
-}
-
 // pointwise flux Jacobians (InviscidFlux::get_jacobian)
 template <int FLUX>
 __global__ __launch_bounds__(256)
@@ -763,101 +398,6 @@ void launch_pseudo_time(int ncell, const double* area, double cfl, double* dtm, 
 {
 	hipLaunchKernelGGL(k_pseudo_time, dim3(nblk(ncell,256)), dim3(256), 0, s, ncell, area, cfl, dtm, diag);
 }
-
-void launch_block_apply(const JacMesh& J, const double* diag, const double* lower, const double* upper,
-                        const double* x, double* y, hipStream_t s)
-{
-	if(J.ncell <= 0) return;
-	if(FVHIP_BLOCK_ROWS)
-		hipLaunchKernelGGL(k_block_apply_rows, dim3(nblk(4LL*J.ncell,256)), dim3(256), 0, s, J, diag, lower, upper, x, y);
-	else
-		hipLaunchKernelGGL(k_block_apply, dim3(nblk(J.ncell,256)), dim3(256), 0, s, J, diag, lower, upper, x, y);
-}
-
-void launch_block_residual(const JacMesh& J, const double* diag, const double* lower, const double* upper,
-                           const double* x, const double* v, double* t, hipStream_t s)
-{
-	if(J.ncell <= 0) return;
-	hipLaunchKernelGGL(k_block_residual_rows<double>, dim3(nblk(4LL*J.ncell,256)), dim3(256), 0, s, J, diag, lower, upper, x, v, t);
-}
-
-void launch_block_residual(const JacMesh& J, const float* diag, const float* lower, const float* upper,
-                           const double* x, const double* v, double* t, hipStream_t s)
-{
-	if(J.ncell <= 0) return;
-	hipLaunchKernelGGL(k_block_residual_rows<float>, dim3(nblk(4LL*J.ncell,256)), dim3(256), 0, s, J, diag, lower, upper, x, v, t);
-}
-
-void launch_bjac_sweep(const JacMesh& J, const double* dinv, const double* lower, const double* upper,
-                       const double* v, const double* zin, double* zout, hipStream_t s)
-{
-	if(J.ncell <= 0) return;
-	if(FVHIP_BLOCK_ROWS)
-		hipLaunchKernelGGL(k_bjac_sweep_rows<double>, dim3(nblk(4LL*J.ncell,256)), dim3(256), 0, s, J, dinv, lower, upper, v, zin, zout);
-	else
-		hipLaunchKernelGGL(k_bjac_sweep<double>, dim3(nblk(J.ncell,256)), dim3(256), 0, s, J, dinv, lower, upper, v, zin, zout);
-}
-void launch_bjac_sweep(const JacMesh& J, const float* dinv, const float* lower, const float* upper,
-                       const double* v, const double* zin, double* zout, hipStream_t s)
-{
-	if(J.ncell <= 0) return;
-	if(FVHIP_BLOCK_ROWS)
-		hipLaunchKernelGGL(k_bjac_sweep_rows<float>, dim3(nblk(4LL*J.ncell,256)), dim3(256), 0, s, J, dinv, lower, upper, v, zin, zout);
-	else
-		hipLaunchKernelGGL(k_bjac_sweep<float>, dim3(nblk(J.ncell,256)), dim3(256), 0, s, J, dinv, lower, upper, v, zin, zout);
-}
-
-template <typename T>
-static void launch_ilu_sweep_solve_t(const JacMesh& J, const int* rank, bool up, const T* dinv, const T* lower, const T* upper,
-                                     const double* w, const double* zin, double* zout, hipStream_t s)
-{
-	if(J.ncell <= 0) return;
-	const dim3 g(nblk(4LL*J.ncell,256)), b(256);
-	if(up) hipLaunchKernelGGL((k_ilu_sweep_solve<T,true>), g, b, 0, s, J, rank, dinv, lower, upper, w, zin, zout);
-	else hipLaunchKernelGGL((k_ilu_sweep_solve<T,false>), g, b, 0, s, J, rank, dinv, lower, upper, w, zin, zout);
-}
-void launch_ilu_sweep_solve(const JacMesh& J, const int* rank, bool up, const double* dinv, const double* lower,
-                            const double* upper, const double* w, const double* zin, double* zout, hipStream_t s)
-{ launch_ilu_sweep_solve_t(J, rank, up, dinv, lower, upper, w, zin, zout, s); }
-void launch_ilu_sweep_solve(const JacMesh& J, const int* rank, bool up, const float* dinv, const float* lower,
-                            const float* upper, const double* w, const double* zin, double* zout, hipStream_t s)
-{ launch_ilu_sweep_solve_t(J, rank, up, dinv, lower, upper, w, zin, zout, s); }
-
-template <typename T>
-void launch_bgs_colour_t(const JacMesh& J, const T* dinv, const T* lower, const T* upper, const double* v,
-                         double* z, const int* cells, int n, hipStream_t s)
-{
-	if(n <= 0) return;
-	if(FVHIP_BLOCK_ROWS)
-		hipLaunchKernelGGL(k_bgs_colour_rows<T>, dim3(nblk(4LL*n,256)), dim3(256), 0, s, J, dinv, lower, upper, v, z, cells, n);
-	else
-		hipLaunchKernelGGL(k_bgs_colour<T>, dim3(nblk(n,256)), dim3(256), 0, s, J, dinv, lower, upper, v, z, cells, n);
-}
-void launch_bgs_colour(const JacMesh& J, const double* dinv, const double* lower, const double* upper,
-                       const double* v, double* z, const int* cells, int n, hipStream_t s)
-{ launch_bgs_colour_t(J, dinv, lower, upper, v, z, cells, n, s); }
-void launch_bgs_colour(const JacMesh& J, const float* dinv, const float* lower, const float* upper,
-                       const double* v, double* z, const int* cells, int n, hipStream_t s)
-{ launch_bgs_colour_t(J, dinv, lower, upper, v, z, cells, n, s); }
-
-void launch_mf_norm(long long n, const double* x, double eps, double* part, double* pm, hipStream_t s)
-{
-	hipLaunchKernelGGL(k_sumsq_partial, dim3(RED_BLOCKS), dim3(256), 0, s, n, x, part);
-	hipLaunchKernelGGL(k_pertmag, dim3(1), dim3(256), 0, s, RED_BLOCKS, part, eps, pm);
-}
-
-void launch_mf_perturb(long long n, const double* u, const double* x, const double* pm, double* aux, hipStream_t s)
-{
-	hipLaunchKernelGGL(k_mf_perturb, dim3(nblk(n,256)), dim3(256), 0, s, n, u, x, pm, aux);
-}
-
-void launch_mf_combine(int ncell, const double* mdt, const double* x, const double* yg, const double* res,
-                       const double* pm, double* y, hipStream_t s)
-{
-	hipLaunchKernelGGL(k_mf_combine, dim3(nblk(ncell,256)), dim3(256), 0, s, ncell, mdt, x, yg, res, pm, y);
-}
-
-int mf_partials() { return RED_BLOCKS; }
 
 void launch_local_jac(int flux, const gd::Gas& G, int nf, const double* ul, const double* ur, const double* n,
                       double* dfdl, double* dfdr, hipStream_t s)

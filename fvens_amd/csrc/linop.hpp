@@ -1,6 +1,7 @@
 /** \file linop.hpp
  * \brief The linear operator and preconditioner of an implicit step on one global system (system.hpp): the
- *   operator and GMRES are in implicit.cpp, the preconditioner in precond.cpp.
+ *   operator and GMRES are in implicit.cpp, the preconditioner in precond.cpp; their kernels in blockops.hip
+ *   (block operator, point-block preconditioners), lines.hip (line-implicit), amg.hip and krylov.hip (vectors).
  */
 #ifndef FVHIP_LINOP_HPP
 #define FVHIP_LINOP_HPP

@@ -20,7 +20,7 @@ inline void checkLineThreshold(double thr) {
 struct PrecondOptions
 {
 	/// the limits the texts of check() name; precond.cpp asserts them equal to KRY_MAXK, AMG_BLOCK_ROWS and
-	/// AMG_BLOCK_ROWS_DEFAULT (krylov.hpp and amg.hpp include the HIP runtime)
+	/// AMG_BLOCK_ROWS_DEFAULT (krylov.hpp, which holds KRY_MAXK, and amg.hpp include the HIP runtime)
 	static constexpr int RESTART_MAX = 128, BLOCK_ROWS_MAX = 2048, BLOCK_ROWS_DEFAULT = 256;
 
 	bool matfree = false;

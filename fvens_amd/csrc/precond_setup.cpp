@@ -208,7 +208,7 @@ LinePlan buildLines(const CellGraph& G, double thr)
 	// lanes: a line of at least LINE_TWIST_MIN cells is solved from both ends (twisted factorisation):
 	// its top half t = (n-1)/2 cells in order, then the twist cell t, on lane j of a twisted group; its
 	// bottom half n-1 .. t+1 in reverse order, then t, on lane j+32. Every other line is one lane of a
-	// group of 64. Rows line-interleaved (krylov.hpp LineSet)
+	// group of 64. Rows line-interleaved (lines.hpp LineSet)
 	const int nl = static_cast<int>(all.size());
 	int ntw = 0;
 	while(ntw < nl && static_cast<int>(all[static_cast<size_t>(ntw)].size()) >= LINE_TWIST_MIN) ntw++;

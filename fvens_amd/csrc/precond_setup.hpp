@@ -77,7 +77,7 @@ struct LinePlan
 	/// the lines as built: cells of line l = line_cells[line_start[l] ..], line_faces = interior face to the
 	/// previous cell, fi << 1 | (previous cell is its R), -1 at a line's first cell
 	std::vector<int> line_start, line_cells, line_faces;
-	/// the same dealt to groups of 64 lanes (krylov.hpp LineSet)
+	/// the same dealt to groups of 64 lanes (lines.hpp LineSet)
 	int twisted_groups = 0, nlines = 0, ngroups = 0, nrows = 0;
 	std::vector<int> gstart, cell, face, len;
 };

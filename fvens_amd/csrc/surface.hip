@@ -9,6 +9,7 @@
  * direction and free-stream pressure come from the host (std::cos / std::sin, as the reference).
  */
 #include "surface.hpp"
+#include "reduce.hpp"
 
 namespace fvhip {
 
@@ -78,24 +79,17 @@ __global__ __launch_bounds__(256)
 void k_entropy_partial(int N, const double* __restrict__ u, const double* __restrict__ area, Gas G, double sinf,
                        double* __restrict__ part)
 {
-	__shared__ double red[256];
 	const int i = blockIdx.x*256 + threadIdx.x;
-	double e = 0.0;
+	double e[1] = {0.0};
 	if(i < N) {
 		double uc[4];
 		const double4 v = reinterpret_cast<const double4*>(u)[i];
 		uc[0] = v.x; uc[1] = v.y; uc[2] = v.z; uc[3] = v.w;
 		const double s = pressure_cons(G, uc)/pow(uc[0], G.g);
 		const double serr = (s - sinf)/sinf;
-		e = serr*serr*area[i];
+		e[0] = serr*serr*area[i];
 	}
-	red[threadIdx.x] = e;
-	__syncthreads();
-	for(int w = 128; w > 0; w >>= 1) {
-		if(static_cast<int>(threadIdx.x) < w) red[threadIdx.x] += red[threadIdx.x + w];
-		__syncthreads();
-	}
-	if(threadIdx.x == 0) part[blockIdx.x] = red[0];
+	block_sum<1>(e, part + blockIdx.x, 1);
 }
 
 __global__ void k_entropy_sum(int nb, const double* __restrict__ part, double* __restrict__ out)

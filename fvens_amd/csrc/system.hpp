@@ -72,6 +72,19 @@ struct System
 			});
 		return tot;
 	}
+	/// the global minimum of every handle's local time steps d_dtm, on the host (the explicit drivers' dtmin):
+	/// per handle launch_min over its owned cells, ncclMin over its ranks and the copy, then the waits and the
+	/// minimum over the handles. -inf if a time step is NaN (launch_min), so the caller's finiteness check fires
+	double allmin() {
+		each([&](size_t, fvhip_ctx* h) {
+			launch_min(h->L.ncell, h->d_dtm, h->iw.part, h->iw.red, h->stream);
+			if(h->comm) NC(ncclAllReduce(h->iw.red, h->iw.red, 1, ncclDouble, ncclMin, h->comm, h->stream));
+			HC(hipMemcpyAsync(h->iw.h_red, h->iw.red, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+		});
+		double m = INFINITY;
+		each([&](size_t, fvhip_ctx* h) { HC(hipStreamSynchronize(h->stream)); m = std::min(m, h->iw.h_red[0]); });
+		return m;
+	}
 	void sync() { each([&](size_t, fvhip_ctx* h) { HC(hipStreamSynchronize(h->stream)); }); }
 	/// one handle: the global sums of the k values in iw.red, copied to iw.h_red2 behind the reduction
 	/// without waiting (read them after a later wait on the stream)
@@ -110,6 +123,33 @@ inline void System::residual(const std::vector<double*>& us) {
 /// the last bits of |x| and stay apart.
 /// have_norm: |x|^2 is already in iw.red (the line solve that produced x summed it, LinOp::precondition)
 void matfreeApply(System& S, const ArrayOf& x, const ArrayOf& y, bool have_norm = false);
+
+typedef std::vector<double*> States;
+
+/// a stepper's entry point on one handle / on a group (implicit.cpp, explicit.cpp): the arguments checked (have:
+/// its other pointers are there), the system made, `step(S, states)` run and waited for
+template <typename F> int onHandle(fvhip_handle h, double* d_u, bool have, F&& step)
+{
+	return guard([&] {
+		need(h, "handle");
+		need(d_u, "u");
+		if(!have) throw std::invalid_argument("null argument");
+		System S = single(h);
+		step(S, States{d_u});
+		S.sync();
+	});
+}
+template <typename F> int onGroup(fvhip_group g, double* const* d_u, bool have, F&& step)
+{
+	return guard([&] {
+		need(g, "group");
+		needEach(d_u, g->hs.size(), "u");
+		if(!have) throw std::invalid_argument("null argument");
+		System S = ofGroup(g);
+		step(S, States(d_u, d_u + S.size()));
+		S.sync();
+	});
+}
 
 }
 #endif

@@ -563,7 +563,7 @@ def line_system():
 
 def line_coverage(lines):
     """(twisted lines, lines of one cell) of a line list; a line of LINE_TWIST_MIN cells or more is solved from both
-    ends, 32 such lines to a group (krylov.hip k_line_factor / k_line_solve)"""
+    ends, 32 such lines to a group (lines.hip k_line_factor / k_line_solve)"""
     lens = np.array([len(c) for c, _ in lines])
     return int((lens >= LINE_TWIST_MIN).sum()), int((lens == 1).sum())
 

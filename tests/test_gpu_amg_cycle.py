@@ -1,5 +1,5 @@
 """The multigrid V-cycle (precond.cpp LinOp::amgApply / cycle; amg.hip k_amg_restrict, k_amg_prolong,
-k_amg_residual; krylov.hip's finest block residual) against a host restatement, on one handle and on the ranks of a
+k_amg_residual; blockops.hip's finest block residual) against a host restatement, on one handle and on the ranks of a
 group (fvhip_group_amg_precondition_smoother_device), where each rank's hierarchy covers its owned cells and only
 the finest residuals couple the ranks.
 

@@ -1,5 +1,5 @@
 """The sweep-based block ILU(0)/SGS preconditioner in a row order (fvhip_implicit_config::ilu_order,
-ilu_build_sweeps = b, ilu_apply_sweeps = a; krylov.hip k_ilu_sweep_factor, jacobian.hip k_ilu_sweep_solve) against
+ilu_build_sweeps = b, ilu_apply_sweeps = a; blockops.hip k_ilu_sweep_factor, k_ilu_sweep_solve) against
 plain-numpy restatements of its formulas, with the order fvhip_ilu_order reports (checked equal to the host shim's,
 tests/test_ilu_order_host.py).
 

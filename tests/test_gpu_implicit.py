@@ -171,7 +171,7 @@ def test_line_solve_inverts_line_blocks(ntheta, nquad, single):
     from the same blocks. 300 quad layers: wall-normal lines cut at 256 cells plus 44-cell remainders,
     solved from both ends (twisted groups of 32 lines), and short lines or lines of one, so a wave's
     lanes walk lines that end at different steps; 21 layers on 48 lines around: odd twisted lines and a
-    half-full twisted group; 10 layers: lines too short to twist (krylov.hip k_line_factor /
+    half-full twisted group; 10 layers: lines too short to twist (lines.hip k_line_factor /
     k_line_solve). single: the factors stored in fp32 (prec_single), |M z - v| <= 1e-5 |v|."""
     torch = _torch()
     m = fa.UMesh.naca_ogrid(ntheta, nquad, 8, 20.0, 1e-6)

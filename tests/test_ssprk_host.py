@@ -69,6 +69,46 @@ def test_vortex_is_a_steady_solution_in_its_frame():
     np.testing.assert_allclose(sh.vortex(b.rc, p0, 10.0), sh.vortex(b.rc, p0, 0.0), rtol=0, atol=1e-13)
 
 
+def test_tvdrk_stage_is_the_rk_stage_with_negated_step():
+    """ode.hip has one stage kernel, k_rk_stage: out = (c0*u + c1*us) + (sc/area)*r. The TVD-RK driver, whose
+    stage the reference writes c0*u + c1*us - (sc/area)*r (aodesolver.cpp:735-744), calls it with -sc. The two are
+    the same bits because (-sc)/area = -(sc/area), (-t)*r = -(t*r) and a + (-x) = a - x are exact in IEEE-754
+    (the kernel is built without contraction, as numpy evaluates here). 1e6 seeded rows whose every operand is
+    drawn from ordinary values, signed zeros, infinities, subnormals, the extremes of the range and values that
+    make the sum cancel; every Shu-Osher (c0, c1) and random ones. Byte for byte, except that where one side is
+    NaN the other must be NaN too (a NaN's sign is not part of the claim)."""
+    rng = np.random.default_rng(20240607)
+    n = 1_000_000
+    tiny = np.finfo(np.float64).tiny
+    special = np.array([0.0, -0.0, np.inf, -np.inf, 5e-324, -5e-324, tiny / 8, -tiny / 8, tiny, -tiny,
+                        np.finfo(np.float64).max, -np.finfo(np.float64).max, 1.0, -1.0])
+
+    def draw(positive=False):
+        x = rng.standard_normal(n) * 10.0 ** rng.integers(-12, 13, n)
+        k = rng.random(n) < 0.3
+        x[k] = special[rng.integers(0, len(special), k.sum())]
+        return np.abs(x) if positive else x
+
+    stages = np.array([(1.0, 0.0), (0.5, 0.5), (0.75, 0.25), (0.3333333333333333, 0.6666666666666667)])
+    c = stages[rng.integers(0, len(stages), n)]
+    k = rng.random(n) < 0.2
+    c[k] = rng.standard_normal((k.sum(), 2))
+    c0, c1 = c[:, 0], c[:, 1]
+    u, us, r, sc, area = draw(), draw(), draw(), draw(), draw(positive=True)
+    # rows that cancel: t*r equal to the sum it is subtracted from, exactly or to the last bits
+    k = rng.random(n) < 0.2
+    with np.errstate(all="ignore"):
+        r[k] = ((c0 * u + c1 * us) / (sc / area))[k] * rng.choice([1.0, 1.0 + 2.0 ** -52, 1.0 - 2.0 ** -53], k.sum())
+        written = c0 * u + c1 * us - (sc / area) * r            # k_tvdrk_stage's expression, as the reference has it
+        called = (c0 * u + c1 * us) + ((-sc) / area) * r        # k_rk_stage with the step negated
+    nan = np.isnan(written)
+    assert np.array_equal(nan, np.isnan(called))
+    assert 0.05 * n < nan.sum() < 0.9 * n                       # the specials reach both kinds of row
+    assert np.count_nonzero(written == 0.0) > 1000 and np.count_nonzero(np.isinf(written)) > 1000
+    same = written.view(np.uint64) == called.view(np.uint64)
+    assert np.all(same | nan), f"{np.count_nonzero(~(same | nan))} rows differ"
+
+
 # --- refusals: checked before the handle, so they answer without a GPU ---------------------------------
 
 def _call(group, cfg, stats=True, handle=None):
