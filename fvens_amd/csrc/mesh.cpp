@@ -1225,7 +1225,8 @@ MeshData generateFlatPlate(int nx, int ny, double xlead, double h, double wallsp
 	const int nlead = std::max(1, nx/8);
 	for(int i = 0; i <= nlead; i++) xs[i] = -xlead*(1.0 - static_cast<double>(i)/nlead);
 	for(int i = nlead; i <= nx; i++) {
-		const double s = static_cast<double>(i - nlead)/(nx - nlead);
+		// nx == nlead (one column: the lead-in alone, ending at the leading edge): 0/0 otherwise
+		const double s = nx > nlead ? static_cast<double>(i - nlead)/(nx - nlead) : 0.0;
 		xs[i] = s*s*(3.0 - 2.0*s)*0.0 + s;                 // uniform on the plate
 	}
 	double lo = 1.0 + 1e-12, hi = 2.0;
