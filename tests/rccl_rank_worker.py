@@ -12,7 +12,12 @@ RCCL unique id and the results; the single-GPU reference results are computed by
 usage (set by the test): RANK, WORLD_SIZE, MASTER_ADDR, MASTER_PORT, NCCL_HOSTID in the environment;
 argv: <out.json> <mesh key> <partitioner> [numerics]  (numerics: "visc" = laminar Roe + WLS + Van Albada +
 Sutherland, "venkat" = Roe + WLS + Venkatakrishnan; "amg" = the implicit steps preconditioned by the multigrid
-(prec_amg 3) and the rank's V-cycle against the group's, without the residual and TVD-RK legs the other rows cover)
+(prec_amg 3) and the rank's V-cycle against the group's, without the residual and TVD-RK legs the other rows cover;
+"functionals" = the surface functionals of markers 2 and 4 and the entropy error over the communicator -- the
+ncclAllReduce that stands for the reference's mpi_all_reduce at flow_spatial.cpp:303 and aoutput.cpp:50 -- laminar at
+3 degrees, beside the one-handle results the rank computes itself, without the residual, implicit and TVD-RK legs)
+partitioner: "graph", "rcb", or "rings" = three bands of equal cell counts by the distance of the cell centre from
+the body, so that rank 0 holds every wall face, rank 2 every far-field face and rank 1 no face of either marker
 """
 import json
 import os
@@ -79,6 +84,37 @@ def amg_cycles(fa, torch, cases, m, p, n, part, sp, g, rank, world):
     return out
 
 
+def partition_rings(m, world):
+    """bands of equal cell counts by the distance of the cell centre from the nearest face centre of marker 2.
+    (The distance from a point does not order the layers of an O-grid round a slender body: about mid-chord the
+    leading- and trailing-edge wall cells lie farther out than the fourteenth layer at mid-chord.)"""
+    wall = np.asarray(m.gr).reshape(-1, 2)[np.nonzero(np.asarray(m.btags).reshape(m.nbface, -1)[:, 0] == 2)[0]]
+    rc = np.asarray(m.rc)[:m.nelem]
+    d = np.sqrt(((rc[:, None, :] - wall[None, :, :]) ** 2).sum(2)).min(1)
+    part = np.empty(m.nelem, np.int32)
+    part[np.argsort(d, kind="stable")] = (np.arange(m.nelem) * world) // m.nelem
+    return part
+
+
+def functionals(torch, cases, m, p, one, sp, g):
+    """markers 2 and 4 and the entropy error on the communicator and on the one handle (state seed 31; the rank's
+    ghost rows start as NaN). Floats go through JSON by repr, which round-trips every bit."""
+    u = cases.state(m, p, seed=31)
+    du1 = torch.tensor(np.ascontiguousarray(u[one.permutation()]), device="cuda")
+    du = torch.full((sp.nown + sp.nghost, 4), float("nan"), dtype=torch.float64, device="cuda")
+    du[:sp.nown] = torch.tensor(u[g], device="cuda")
+    torch.cuda.synchronize()
+    out = {}
+    for marker in (2, 4):
+        f1, rows1 = one.surface_data_device(du1.data_ptr(), marker)
+        f, rows = sp.surface_data_device(du.data_ptr(), marker)
+        out["marker%d" % marker] = {"funcs": list(f), "rows": rows.tolist(), "one_funcs": list(f1),
+                                    "one_rows": rows1.tolist()}
+    out["entropy"] = sp.entropy_error_device(du.data_ptr())
+    out["one_entropy"] = one.entropy_error_device(du1.data_ptr())
+    return out
+
+
 def main():
     out_path, meshkey, partitioner = sys.argv[1], sys.argv[2], sys.argv[3]
     mode = sys.argv[4] if len(sys.argv) > 4 else ""
@@ -95,9 +131,18 @@ def main():
     from test_gpu_residual import get_mesh
 
     m, _ = get_mesh(meshkey)
-    p = cases.physics("visc" if mode == "visc" else "naca")
+    p = cases.physics("visc", aoa_deg=3.0) if mode == "functionals" else cases.physics("visc" if mode == "visc" else "naca")
     n = cases.numerics("ROE", "LEASTSQUARES", "VENKATAKRISHNAN" if mode == "venkat" else "VANALBADA")
-    part = fa.partition_graph(m, world, weights="cost") if partitioner == "graph" else fa.partition_rcb(m, world)
+    if partitioner == "rings":
+        part = partition_rings(m, world)
+        # before the first collective, from what every rank holds: who owns the faces of each marker
+        tags = np.asarray(m.btags).reshape(m.nbface, -1)[:, 0]
+        held = {k: np.bincount(part[m.intfac[np.nonzero(tags == k)[0], 0]], minlength=world) for k in (2, 4)}
+        assert world == 3 and held[2][1] == held[2][2] == 0 and held[4][0] == held[4][1] == 0, held
+        assert held[2][0] == (tags == 2).sum() > 0 and held[4][2] == (tags == 4).sum() > 0, held
+        assert np.bincount(part, minlength=world).tolist() == [m.nelem // world] * world
+    else:
+        part = fa.partition_graph(m, world, weights="cost") if partitioner == "graph" else fa.partition_rcb(m, world)
     amg = mode == "amg"
     # before the first collective, from the partition every rank holds: a rank whose cells do not coarsen would
     # throw inside the solve while the others wait in an allreduce
@@ -125,6 +170,17 @@ def main():
     sp.comm_init(world, rank, uid())
     g = owned[sp.permutation()]
     p1 = one.permutation()
+    if mode == "functionals":
+        rep["layout"] = sp.layout_stats()
+        rep["functionals"] = functionals(torch, cases, m, p, one, sp, g)
+        mark("functionals done")
+        sp.close()
+        one.close()
+        with open(out_path, "w") as f:
+            json.dump(rep, f)
+        dist.barrier()
+        dist.destroy_process_group()
+        return
     bad = 0
     for k in range(0 if amg else 5):
         u = cases.state(m, p, seed=20 + k)
