@@ -142,6 +142,23 @@ def _ssprk(call, order, finaltime, maxsteps, cfl, dt, record):
     return stats, (rec[:stats["steps"]] if record else None)
 
 
+def _bdf(call, order, finaltime, maxsteps, cfg, cfl, dt, record):
+    """runs one of the fvhip_*bdf_device entry points: call(config, implicit config, stats, dual-time stats, record
+    pointer or None); returns (stats dict: the ssprk drivers' keys and inner_iters, inner_max, inner_unconverged,
+    worst_ratio, lin_iters, lin_unconverged; record rows [steps][8] = t after the step, h, inner iterations, final
+    g/g0, sum area*(rho, rho u, rho v, E); None if not asked)"""
+    c = _ffi.FvUnsteadyConfig(int(order), float(cfl), float(dt), float(finaltime), int(maxsteps))
+    ic = cfg._struct()
+    st, ds = _ffi.FvUnsteadyStats(), _ffi.FvDualTimeStats()
+    rec = np.zeros((max(int(maxsteps), 1), 8)) if record else None
+    check(call(ctypes.byref(c), ctypes.byref(ic), ctypes.byref(st), ctypes.byref(ds), dptr(rec) if record else None))
+    stats = dict(steps=int(st.steps), time=float(st.time), dt_min=float(st.dt_min), dt_max=float(st.dt_max),
+                 cfl_max=float(st.cfl_max), inner_iters=int(ds.inner_iters), inner_max=int(ds.inner_max),
+                 inner_unconverged=int(ds.inner_unconverged), worst_ratio=float(ds.worst_ratio),
+                 lin_iters=int(ds.lin_iters), lin_unconverged=int(ds.lin_unconverged))
+    return stats, (rec[:stats["steps"]] if record else None)
+
+
 class UMesh:
     """Reference-indexed mesh built natively (mesh/mesh.hpp accessors as numpy arrays)."""
 
@@ -489,6 +506,30 @@ class FlowFV:
         steps, time, dt_min, dt_max, cfl_max; the record rows taken [steps][6], or None without record)"""
         return _ssprk(lambda c, st, rec: _ffi.lib().fvhip_ssprk_device(self._h, ctypes.c_void_p(d_u), c, st, rec),
                       order, finaltime, maxsteps, cfl, dt, record)
+
+    def bdf_device(self, d_u, order, finaltime, maxsteps, cfg: ImplicitConfig, cfl=0.0, dt=0.0, record=False):
+        """implicit time-accurate stepping on the device (fvhip_bdf_device): BDF1 or variable-step BDF2 in dual
+        time, lands on finaltime; one of cfl (h = cfl dtmin) and dt (fixed step); cfg.tol and cfg.maxiter are the
+        inner tolerance and cap. Returns (stats dict, the record rows taken [steps][8] or None), see _bdf"""
+        return _bdf(lambda c, ic, st, ds, rec: _ffi.lib().fvhip_bdf_device(self._h, ctypes.c_void_p(d_u), c, ic, st, ds,
+                                                                           rec),
+                    order, finaltime, maxsteps, cfg, cfl, dt, record)
+
+    def bdf_residual_device(self, d_u, d_un, d_um, a0, a1, a2, h, d_g):
+        """the unsteady residual of a BDF step alone (fvhip_bdf_residual_device): the residual at d_u, then
+        d_g = residual - (area/h)*((a0 u + a1 un) + a2 um); d_um may be None (0) when a2 == 0. Returns
+        sum area * sum_v g^2 over all owned cells"""
+        s = np.zeros(1)
+        check(_ffi.lib().fvhip_bdf_residual_device(self._h, ctypes.c_void_p(d_u), ctypes.c_void_p(d_un),
+                                                   ctypes.c_void_p(d_um or None), float(a0), float(a1), float(a2),
+                                                   float(h), ctypes.c_void_p(d_g), dptr(s)))
+        return float(s[0])
+
+    def add_physical_time_term_device(self, s, d_mdt, d_diag):
+        """d_mdt += s*area and the same on the four diagonal entries of every block of d_diag (s = a0/h of a BDF
+        step), after add_pseudo_time_term_device"""
+        check(_ffi.lib().fvhip_add_physical_time_term_device(self._h, float(s), ctypes.c_void_p(d_mdt),
+                                                             ctypes.c_void_p(d_diag)))
 
     def steady_backward_euler_device(self, d_u, cfg: ImplicitConfig):
         """SteadyBackwardEulerSolver::solve on the device (aodesolver.cpp:363-638), linear systems by
@@ -858,6 +899,12 @@ class FlowFVGroup:
         ptrs = self._ptrs(d_us)
         return _ssprk(lambda c, st, rec: _ffi.lib().fvhip_group_ssprk_device(self._g, ptrs, c, st, rec),
                       order, finaltime, maxsteps, cfl, dt, record)
+
+    def bdf_device(self, d_us, order, finaltime, maxsteps, cfg: ImplicitConfig, cfl=0.0, dt=0.0, record=False):
+        """FlowFV.bdf_device over the group: one global time step and inner norm, the record's sums over all ranks"""
+        ptrs = self._ptrs(d_us)
+        return _bdf(lambda c, ic, st, ds, rec: _ffi.lib().fvhip_group_bdf_device(self._g, ptrs, c, ic, st, ds, rec),
+                    order, finaltime, maxsteps, cfg, cfl, dt, record)
 
     def steady_backward_euler_device(self, d_us, cfg: ImplicitConfig):
         st = _ffi.FvSolveStats()

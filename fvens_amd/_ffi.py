@@ -64,6 +64,11 @@ class FvUnsteadyStats(ctypes.Structure):
                 ("dt_max", ctypes.c_double), ("cfl_max", ctypes.c_double)]
 
 
+class FvDualTimeStats(ctypes.Structure):
+    _fields_ = [("inner_iters", ctypes.c_int), ("inner_max", ctypes.c_int), ("inner_unconverged", ctypes.c_int),
+                ("worst_ratio", ctypes.c_double), ("lin_iters", ctypes.c_int), ("lin_unconverged", ctypes.c_int)]
+
+
 _vpp = ctypes.POINTER(ctypes.c_void_p)
 
 # name -> (restype, argtypes); kept in sync with include/fvhip.h (tests check every symbol)
@@ -128,6 +133,16 @@ _SIGS = {
                                           ctypes.POINTER(FvUnsteadyStats), c_dbl_p]),
     "fvhip_group_ssprk_device": (ctypes.c_int, [ctypes.c_void_p, _vpp, ctypes.POINTER(FvUnsteadyConfig),
                                                 ctypes.POINTER(FvUnsteadyStats), c_dbl_p]),
+    "fvhip_bdf_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(FvUnsteadyConfig),
+                                        ctypes.POINTER(FvImplicitConfig), ctypes.POINTER(FvUnsteadyStats),
+                                        ctypes.POINTER(FvDualTimeStats), c_dbl_p]),
+    "fvhip_group_bdf_device": (ctypes.c_int, [ctypes.c_void_p, _vpp, ctypes.POINTER(FvUnsteadyConfig),
+                                              ctypes.POINTER(FvImplicitConfig), ctypes.POINTER(FvUnsteadyStats),
+                                              ctypes.POINTER(FvDualTimeStats), c_dbl_p]),
+    "fvhip_bdf_residual_device": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_double] * 4 +
+                                  [ctypes.c_void_p, c_dbl_p]),
+    "fvhip_add_physical_time_term_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p,
+                                                           ctypes.c_void_p]),
     "fvhip_steady_backward_euler_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p,
                                                           ctypes.POINTER(FvImplicitConfig),
                                                           ctypes.POINTER(FvSolveStats), c_dbl_p]),

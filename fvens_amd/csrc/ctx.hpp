@@ -138,6 +138,10 @@ struct fvhip_ctx
 	const double *mf_u = nullptr, *mf_r = nullptr, *mf_mdt = nullptr;   // device state of the operator
 	double *d_part = nullptr, *d_pm = nullptr;
 	double* d_stage = nullptr;                       // Runge-Kutta stage state (owned + ghost rows: SSP-RK's is a residual's input)
+	/// BDF dual time (implicit.cpp dualTime), owned rows each: the states u^n and u^(n-1), whose pointers trade
+	/// places at the start of a step, and the unsteady residual G (d_r stays the spatial residual: the matrix-free
+	/// operator differences it)
+	double *d_bdf_n = nullptr, *d_bdf_m = nullptr, *d_bdf_g = nullptr;
 	double* d_ent = nullptr;                        // entropy-error partial sums (fvhip_entropy_error_device)
 	/// work space of the implicit solver (implicit.cpp), allocated on first use
 	struct ImplicitWork {

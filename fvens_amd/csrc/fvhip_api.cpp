@@ -586,6 +586,17 @@ int fvhip_add_pseudo_time_term_device(fvhip_handle h, double cfl, double* d_dtm,
 	});
 }
 
+int fvhip_add_physical_time_term_device(fvhip_handle h, double s, double* d_mdt, double* d_diag)
+{
+	return guard([&] {
+		need(h, "handle");
+		need(d_mdt, "mdt"); need(d_diag, "diag");
+		HC(hipSetDevice(h->device));
+		h->timed("k_bdf_time_term", [&]{ launch_bdf_time_term(h->L.ncell, s, h->M.area, d_mdt, d_diag, h->stream); });
+		HC(hipGetLastError());
+	});
+}
+
 int fvhip_block_apply_device(fvhip_handle h, const double* d_diag, const double* d_lower, const double* d_upper,
                              const double* d_x, double* d_y)
 {

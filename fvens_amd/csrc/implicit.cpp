@@ -1,7 +1,8 @@
 /** \file implicit.cpp
  * \brief The device-resident implicit pseudo-time solver over one global system:
  *   SteadyBackwardEulerSolver::solve (aodesolver.cpp:363-638), its GMRES and the matrix-free operator over a
- *   system. The explicit drivers are in explicit.cpp.
+ *   system, and the implicit time-accurate driver round the same iteration (dualTime: BDF1/BDF2 in dual time).
+ *   The explicit drivers are in explicit.cpp.
  *
  * The reference hands each linear system to PETSc (KSPSolve, aodesolver.cpp:483; GMRES with a
  * block-Jacobi/ILU or SOR preconditioner from the .solverc files). Here it is solved on the device
@@ -276,11 +277,181 @@ static void backwardEuler(System& S, const std::vector<double*>& us, const fvhip
 	st->lin_worst = linworst;
 }
 
+/// a step that would end within this fraction of itself before finaltime is stretched to land on it (dualTime)
+static const double BDF_SLIVER = 1e-9;
+
+/// the dual-time driver's arguments, refused by name before any handle or device is touched
+static void checkDualTime(const fvhip_unsteady_config* c, const fvhip_implicit_config* ic, const fvhip_unsteady_stats* st,
+                          const fvhip_dualtime_stats* ds)
+{
+	need(c, "config");
+	need(ic, "implicit config");
+	need(st, "stats");
+	need(ds, "dual-time stats");
+	if(c->order < 1 || c->order > 2) throw std::invalid_argument("BDF: temporal order must be 1 or 2");
+	if(c->maxsteps < 1) throw std::invalid_argument("BDF: maxsteps must be >= 1");
+	if(!(c->finaltime > 0.0)) throw std::invalid_argument("BDF: finaltime must be > 0");
+	if((c->cfl > 0.0) == (c->dt > 0.0))
+		throw std::invalid_argument("BDF: exactly one of cfl > 0 and dt > 0 must be given");
+	if(ic->maxiter < 1) throw std::invalid_argument("BDF: maxiter (inner iterations per step) must be >= 1");
+	if(ic->resume_res0 > 0.0 || ic->resume_res > 0.0 || ic->resume_res_prev > 0.0 || ic->resume_cfl > 0.0)
+		throw std::invalid_argument("BDF: resume_* continues a steady solve; the inner iteration starts anew every step");
+}
+
+/// Implicit time-accurate stepping in dual time: BDF1, or BDF2 with variable step (its first step is BDF1).
+/// d_r = -r(u) as the residual leaves it, so area du/dt = d_r and one physical step of size h finds u with
+///   G(u) = d_r(u) - (area/h)*((a0*u + a1*u^n) + a2*u^(n-1)) = 0          (k_bdf_residual, ode.hip)
+/// BDF1: a = (1, -1, 0). BDF2 with w = h/h_prev: a0 = (1+2w)/(1+w), a1 = -(1+w), a2 = w^2/(1+w).
+/// G = 0 is solved by backwardEuler's pseudo-time iteration applied to G, from u = u^n: per inner iteration
+///   [(m + s area) I + dr/du] du = G(u),   m = area/(cfl_tau dtm),  s = a0/h
+/// which is the steady system with b = G and m + s area where it has m -- in the diagonal blocks and in d_dtm,
+/// the matrix-free operator's mdt (k_bdf_time_term after the assembly). The matrix-free operator differences the
+/// spatial residual, so d_r stays that and G has a buffer of its own.
+/// Per step: d_r, d_dtm at u^n; dtmin as ssprk reads it; h = dt or cfl dtmin, set to finaltime - t when t + h
+/// reaches finaltime or ends within BDF_SLIVER h of it (that step has w != 1). Then: G and g = sqrt(sum area sum_v G^2) at the current u; stop
+/// when g <= tol g0 (g0: the step's first g; g0 == 0 leaves the state as it is) or after maxiter solves, else ramp
+/// the pseudo CFL on g_old/g from cflinit, assemble, add the time term, set up the preconditioner, solve, update.
+/// The test comes before the solve, so the returned state is the one whose G was measured.
+/// record [maxsteps][8] (host, may be null): t after the step, h, inner iterations, final g/g0, sum area u.
+static void dualTime(System& S, const std::vector<double*>& us, const fvhip_unsteady_config& c,
+                     const fvhip_implicit_config& ic, fvhip_unsteady_stats* st, fvhip_dualtime_stats* ds, double* record)
+{
+	LinOp A{S, PrecondOptions::of(ic)};
+	A.o.check();
+	S.each([&](size_t, fvhip_ctx* h) {
+		h->ensureImplicit(ic.restart);
+		h->mf_eps = ic.mf_eps;
+		if(!h->d_bdf_g) {
+			const size_t n4 = 4*static_cast<size_t>(h->L.ncell);
+			h->d_bdf_n = dalloc(n4, h->owned); h->d_bdf_m = dalloc(n4, h->owned); h->d_bdf_g = dalloc(n4, h->owned);
+		}
+	});
+	for(fvhip_ctx* h : S.hs) { A.D.push_back(h->iw.jd); A.Lo.push_back(h->iw.jlo); A.Up.push_back(h->iw.jup); }
+	const ArrayOf bs = [&](size_t i) { return S.hs[i]->d_bdf_g; };
+	const ArrayOf xs = [&](size_t i) { return S.hs[i]->iw.du; };
+	const char* diverged = "BDF dual time diverged - residual is Nan or inf!";
+
+	int step = 0;
+	double time = 0, hprev = 0, hmin = INFINITY, hmax = 0, cflmax = 0;
+	*ds = fvhip_dualtime_stats{};
+	while(time < c.finaltime && step < c.maxsteps) {
+		S.each([&](size_t i, fvhip_ctx* h) {                                    // u^(n-1) <- u^n, u^n <- u
+			std::swap(h->d_bdf_n, h->d_bdf_m);
+			HC(hipMemcpyAsync(h->d_bdf_n, us[i], sizeof(double)*4*static_cast<size_t>(h->L.ncell),
+			                  hipMemcpyDeviceToDevice, h->stream));
+		});
+		S.residual(us);                                                         // -r(u^n), local time steps
+		const double dtmin = S.allmin();
+		if(!std::isfinite(dtmin)) throw std::runtime_error(diverged);           // a NaN state: its time step is NaN
+		double dt = c.dt > 0.0 ? c.dt : c.cfl*dtmin;
+		// the last step: ssprk's test, and also when the step would leave a remainder of rounding size (ten steps of
+		// 0.2 sum to 2 - 2^-52). A step of that size has w ~ 1e-15, and the rounding of a0 + a1 times u/h is O(1) in G
+		const bool last = time + dt >= c.finaltime || c.finaltime - (time + dt) <= BDF_SLIVER*dt;
+		if(last) dt = c.finaltime - time;
+		double a0 = 1.0, a1 = -1.0, a2 = 0.0;
+		if(c.order == 2 && step > 0) {
+			const double w = dt/hprev;
+			a0 = (1.0 + 2.0*w)/(1.0 + w); a1 = -(1.0 + w); a2 = w*w/(1.0 + w);
+		}
+		const double s = a0/dt;
+
+		double g = 0, g0 = 0, gold = 0, curCFL = 0;
+		int k = 0;
+		while(true) {
+			if(k > 0) S.residual(us);
+			S.each([&](size_t i, fvhip_ctx* h) {
+				launch_bdf_residual(h->L.ncell, a0, a1, a2, dt, h->M.area, h->d_r, us[i], h->d_bdf_n,
+				                    a2 != 0.0 ? h->d_bdf_m : nullptr, h->d_bdf_g, h->iw.part, h->iw.red, h->stream);
+				HC(hipGetLastError());
+			});
+			gold = g;
+			g = std::sqrt(S.allsum(1, false)[0]);
+			if(!std::isfinite(g)) throw std::runtime_error(diverged);
+			if(k == 0) { g0 = gold = g; if(g0 == 0.0) break; }
+			if(g <= ic.tol*g0 || k >= ic.maxiter) break;
+			curCFL = expResidualRamp(ic.cflinit, ic.cflfin, curCFL, gold/g, 0.25, 0.3);
+			S.each([&](size_t i, fvhip_ctx* h) {
+				h->assemble(us[i], h->iw.jd, h->iw.jlo, h->iw.jup, curCFL, h->d_dtm);
+				h->timed("k_bdf_time_term", [&]{ launch_bdf_time_term(h->L.ncell, s, h->M.area, h->d_dtm, h->iw.jd, h->stream); });
+				HC(hipGetLastError());
+			});
+			A.setup();
+			if(A.o.matfree)
+				S.each([&](size_t i, fvhip_ctx* h) { h->mf_u = us[i]; h->mf_r = h->d_r; h->mf_mdt = h->d_dtm; });
+			const GmresOut lin = gmres(S, A, bs, xs, ic.lin_rtol, ic.lin_maxit, ic.restart, ic.cgs_refine);
+			ds->lin_iters += lin.iters;
+			if(lin.rnorm0 > 0.0 && lin.rnorm > ic.lin_rtol*lin.rnorm0) ds->lin_unconverged++;
+			S.each([&](size_t i, fvhip_ctx* h) {
+				launch_relaxed_update(h->L.ncell, h->P.gas, ic.min_relax, h->iw.du, us[i], h->stream);
+				HC(hipGetLastError());
+			});
+			k++;
+		}
+		const double ratio = g0 > 0.0 ? g/g0 : 0.0;
+		ds->inner_iters += k;
+		ds->inner_max = std::max(ds->inner_max, k);
+		if(g0 > 0.0 && g > ic.tol*g0) ds->inner_unconverged++;
+		ds->worst_ratio = std::max(ds->worst_ratio, ratio);
+
+		time = last ? c.finaltime : time + dt;
+		hprev = dt;
+		hmin = std::min(hmin, dt); hmax = std::max(hmax, dt); cflmax = std::max(cflmax, dt/dtmin);
+		if(record) {
+			S.each([&](size_t i, fvhip_ctx* h) {
+				launch_conserved(h->L.ncell, us[i], h->M.area, h->iw.part, h->iw.red, h->stream);
+				HC(hipGetLastError());
+			});
+			const std::vector<double> sums = S.allsum(4, false);
+			double* row = record + 8*static_cast<size_t>(step);
+			row[0] = time; row[1] = dt; row[2] = k; row[3] = ratio;
+			std::copy(sums.begin(), sums.end(), row + 4);
+		}
+		step++;
+	}
+	if(A.o.matfree) S.each([&](size_t, fvhip_ctx* h) { h->mf_u = h->mf_r = h->mf_mdt = nullptr; });
+	st->steps = step;
+	st->time = time;
+	st->dt_min = hmin; st->dt_max = hmax; st->cfl_max = cflmax;
+}
+
 }
 
 using namespace fvhip_detail;
 
 extern "C" {
+
+int fvhip_bdf_device(fvhip_handle h, double* d_u, const fvhip_unsteady_config* cfg, const fvhip_implicit_config* icfg,
+                     fvhip_unsteady_stats* stats, fvhip_dualtime_stats* dstats, double* record)
+{
+	if(guard([&] { checkDualTime(cfg, icfg, stats, dstats); })) return 1;
+	return onHandle(h, d_u, true, [&](System& S, const States& us) { dualTime(S, us, *cfg, *icfg, stats, dstats, record); });
+}
+
+int fvhip_group_bdf_device(fvhip_group g, double* const* d_u, const fvhip_unsteady_config* cfg,
+                           const fvhip_implicit_config* icfg, fvhip_unsteady_stats* stats, fvhip_dualtime_stats* dstats,
+                           double* record)
+{
+	if(guard([&] { checkDualTime(cfg, icfg, stats, dstats); })) return 1;
+	return onGroup(g, d_u, true, [&](System& S, const States& us) { dualTime(S, us, *cfg, *icfg, stats, dstats, record); });
+}
+
+int fvhip_bdf_residual_device(fvhip_handle h, double* d_u, const double* d_un, const double* d_um, double a0, double a1,
+                              double a2, double hstep, double* d_g, double* sumsq)
+{
+	if(guard([&] {
+		need(d_un, "un"); need(d_g, "g"); need(sumsq, "sumsq");
+		if(a2 != 0.0) need(d_um, "um");
+		if(!(hstep > 0.0)) throw std::invalid_argument("BDF residual: the step must be > 0");
+	})) return 1;
+	return onHandle(h, d_u, true, [&](System& S, const States& us) {
+		h->ensureReductions();
+		S.residual(us);
+		launch_bdf_residual(h->L.ncell, a0, a1, a2, hstep, h->M.area, h->d_r, d_u, d_un, a2 != 0.0 ? d_um : nullptr, d_g,
+		                    h->iw.part, h->iw.red, h->stream);
+		HC(hipGetLastError());
+		*sumsq = S.allsum(1, false)[0];
+	});
+}
 
 int fvhip_steady_backward_euler_device(fvhip_handle h, double* d_u, const fvhip_implicit_config* cfg,
                                        fvhip_solve_stats* stats, double* reshistory)

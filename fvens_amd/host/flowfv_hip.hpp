@@ -294,6 +294,34 @@ private:
 	bool keep;
 };
 
+/// The time-accurate implicit solver (fvhip_bdf_device): BDF1 or variable-step BDF2 in dual time, landing on
+/// finaltime. Constructed like SSPRKSolver_HIP with (temporal order 1 or 2, physical CFL) and the implicit
+/// configuration of the inner pseudo-time iteration (tol, maxiter: inner tolerance and cap); fixed_dt > 0 takes
+/// that step instead of cfl * dtmin. keep_record: one row per step in `record`
+class BDFSolver_HIP
+{
+public:
+	BDFSolver_HIP(const FlowFV_HIP* s, int temporal_order, double cfl_num, int max_steps, const fvhip_implicit_config& inner_cfg,
+	              double fixed_dt = 0.0, bool keep_record = false)
+		: spatial(s), conf{temporal_order, fixed_dt > 0.0 ? 0.0 : cfl_num, fixed_dt, 0.0, max_steps}, iconf(inner_cfg),
+		  keep(keep_record) { }
+	StatusCode solve(double* d_u, double finaltime) {
+		conf.finaltime = finaltime;
+		record.assign(keep && conf.maxsteps > 0 ? 8*static_cast<size_t>(conf.maxsteps) : 0, 0.0);
+		check(fvhip_bdf_device(spatial->handle(), d_u, &conf, &iconf, &stats, &inner, keep ? record.data() : nullptr));
+		record.resize(keep ? 8*static_cast<size_t>(stats.steps) : 0);
+		return 0;
+	}
+	fvhip_unsteady_stats stats{};
+	fvhip_dualtime_stats inner{};  ///< inner iterations, steps that ended at the cap, the worst final g/g0
+	std::vector<double> record;   ///< [steps][8]: t after the step, h, inner iterations, final g/g0, sum area*(rho, rho u, rho v, E)
+private:
+	const FlowFV_HIP* spatial;
+	fvhip_unsteady_config conf;
+	fvhip_implicit_config iconf;
+	bool keep;
+};
+
 /// Batched InviscidFlux::get_flux / get_jacobian on the device (anumericalflux.hpp:32-45)
 class InviscidFlux_HIP
 {

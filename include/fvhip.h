@@ -251,6 +251,10 @@ int fvhip_assemble_jacobian_device(fvhip_handle h, const double* d_u, double* d_
 /** SteadyBackwardEulerSolver::addPseudoTimeTerm (aodesolver.cpp:300-329) on device arrays:
  *  d_dtm <- area/(cfl*d_dtm); d_diag += d_dtm * I */
 int fvhip_add_pseudo_time_term_device(fvhip_handle h, double cfl, double* d_dtm, double* d_diag);
+/** Its counterpart for a physical time step (fvhip_bdf_device), after it: d_mdt += s*area; the same product
+ *  added to the four diagonal entries of every block of d_diag. s = a0/h of the BDF step. d_mdt then is what the
+ *  matrix-free operator takes as mdt. */
+int fvhip_add_physical_time_term_device(fvhip_handle h, double s, double* d_mdt, double* d_diag);
 /** y = A x with the face-based blocks (the product PETSc's MatMult forms, alinalg.cpp:90-119) */
 int fvhip_block_apply_device(fvhip_handle h, const double* d_diag, const double* d_lower,
                              const double* d_upper, const double* d_x, double* d_y);
@@ -416,6 +420,50 @@ int fvhip_steady_backward_euler_device(fvhip_handle h, double* d_u, const fvhip_
                                        fvhip_solve_stats* stats, double* reshistory);
 int fvhip_group_steady_backward_euler_device(fvhip_group g, double* const* d_u, const fvhip_implicit_config* cfg,
                                              fvhip_solve_stats* stats, double* reshistory);
+/** Implicit time-accurate driver: BDF1 or variable-step BDF2 in dual time. The residual assembles -r(u), so
+ *  area du/dt = residual, and one physical step of size h from u^n (and u^(n-1)) finds u with
+ *    G(u) = residual(u) - (area/h) * ((a0 u + a1 u^n) + a2 u^(n-1)) = 0
+ *  BDF1 (order 1): a = (1, -1, 0). BDF2 (order 2) with w = h/h_prev: a0 = (1+2w)/(1+w), a1 = -(1+w),
+ *  a2 = w^2/(1+w), i.e. (3/2, -2, 1/2) at equal steps; its first step is a BDF1 step. The caller keeps step ratios
+ *  below 1 + sqrt 2 (zero-stability of variable-step BDF2; not checked).
+ *  G = 0 is solved by the pseudo-time iteration of fvhip_steady_backward_euler_device applied to G from u = u^n:
+ *  per inner iteration [(m + a0/h area) I + dr/du] du = G with m = area/(cfl_tau dtm) the pseudo-time term, then the
+ *  relaxed update. The inner loop measures g = sqrt(sum_cells area sum_v G^2) at the current state and stops, before
+ *  solving, when g <= tol g0 (g0: its first value in the step) or after maxiter solves: the state returned is the one
+ *  whose G was measured. g0 == 0 ends the step with no iteration and the state untouched. A non-finite g or dtmin
+ *  ends the run with "BDF dual time diverged - residual is Nan or inf!".
+ *  cfg: order 1 or 2; h = dt if dt > 0, else cfl * dtmin at the step's start state (exactly one of them); a step
+ *  with t + h >= finaltime is cut to finaltime - t and the time returned is finaltime exactly; so is a step that
+ *  would end within 1e-9 h before finaltime (ten steps of 0.2 sum to 2 - 2^-52: the remainder is not a step, and
+ *  with a step ratio of 1e-15 the rounding of a0 + a1 would dominate G); maxsteps caps the run.
+ *  icfg: tol and maxiter are the inner tolerance and cap; cflinit, cflfin bound the pseudo CFL, ramped on g_old/g
+ *  from cflinit in every physical step; matrix_free, the preconditioners and the linear-solver options as in the
+ *  steady solver (the assembled first-order operator only slows the inner iteration: accuracy in time depends on
+ *  how far G is driven down, not on the Jacobian); resume_* must be 0.
+ *  stats: as fvhip_ssprk_device. dstats: the inner iterations. record (host, [maxsteps][8], may be NULL): per step
+ *  the time after it, h, the inner iterations, the final g/g0, and the sums of area * u over all owned cells of all
+ *  ranks for (rho, rho u, rho v, E). The history u^n, u^(n-1) is the handle's; every call starts with a BDF1 step. */
+typedef struct fvhip_dualtime_stats {
+	int inner_iters;          /* inner (pseudo-time) iterations over all steps */
+	int inner_max;            /* most inner iterations of one step */
+	int inner_unconverged;    /* steps that ended at maxiter with g > tol g0 */
+	double worst_ratio;       /* largest final g/g0 over the steps */
+	int lin_iters;            /* total Krylov iterations */
+	int lin_unconverged;      /* linear solves that stopped at lin_maxit above lin_rtol */
+} fvhip_dualtime_stats;
+int fvhip_bdf_device(fvhip_handle h, double* d_u, const fvhip_unsteady_config* cfg, const fvhip_implicit_config* icfg,
+                     fvhip_unsteady_stats* stats, fvhip_dualtime_stats* dstats, double* record);
+int fvhip_group_bdf_device(fvhip_group g, double* const* d_u, const fvhip_unsteady_config* cfg,
+                           const fvhip_implicit_config* icfg, fvhip_unsteady_stats* stats, fvhip_dualtime_stats* dstats,
+                           double* record);
+/** The unsteady residual alone, for a caller that keeps its own time loop: the residual at d_u (device state in
+ *  internal order, with room for the ghost rows on partitioned and periodic handles, which are filled), then
+ *  d_g = residual - (area/hstep) * ((a0 d_u + a1 d_un) + a2 d_um) on the owned rows, in that association, and
+ *  *sumsq = sum over the owned cells of all ranks of area * sum_v g^2, reduced in a fixed order. d_um is read only
+ *  when a2 != 0 and may be NULL otherwise. The handle's residual scratch is overwritten. */
+int fvhip_bdf_residual_device(fvhip_handle h, double* d_u, const double* d_un, const double* d_um, double a0, double a1,
+                              double a2, double hstep, double* d_g, double* sumsq);
+
 /** The linear solver alone: GMRES(restart) with `sweeps` block-Jacobi sweeps as right preconditioner
  *  on the block operator (d_diag internal order [ncell][16], d_lower/d_upper [ninface][16]); solves
  *  A x = b from x = 0 until |b - A x| <= rtol |b| or maxit iterations */
